@@ -13,6 +13,11 @@ under torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the 
 WORLD_SIZE is unset and N > 1, bench.py starts that launcher itself as a child process
 before anything touches a GPU.  --dry-run exercises the launch / strip / gather / check
 plumbing on CPU ranks over gloo with synthetic pattern strips (no GPU, no renderer).
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --dump-outputs DIR
+also writes the last timed frame to DIR/image.npy.  --full adds, after the timed steps, everything
+the headline figure does not need: the sync and moving-camera legs, the roofline, the max |dpixel|
+check against the oracle and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -43,6 +48,7 @@ WIDE_NODE_BYTES = 160        # one wide-BVH node visit reads the 128-B node and 
                              # (8 + 2 x 16-B loads)
 CERT_BYTES = 72              # one certificate: the octree leaf's 64-B node + two 4-B slot maps
 PIXEL_BYTES = 4              # ARGB32 write per internal pixel
+KERNEL_TIMES_RING = 256      # rt_kernel_times answers for at most this many launches (renderer.hpp EV_RING)
 COUNTS_FILE = os.path.join(ROOT, "profiles", "work_counts.json")
 # configs whose oracle frame takes minutes on the host (hair1m: ~100 s on 8 threads): bench checks
 # every CHECK_STRIDE-th output row (its f internal rows) instead of the whole frame
@@ -68,6 +74,13 @@ def parse():
     ap.add_argument("--no-balance", dest="balance", action="store_false",
                     help="N > 1: keep the interleaved bands (default: cost-balanced band lists after the warm-up)")
     ap.add_argument("--no-legs", action="store_true", help="N = 1: skip the sync and moving-camera legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the sync and "
+                         "moving-camera legs, the roofline, the max |dpixel| check against the oracle and the CPU "
+                         "baseline (--no-legs / --no-check / --no-cpu-baseline drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last timed step's frame to DIR/image.npy: float32 "
+                         "[height, width, 4], the A, R, G, B bytes of every ARGB32 pixel")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU ranks over gloo, synthetic pattern strips: the launch / gather / check plumbing only")
     return ap.parse_args()
@@ -107,6 +120,16 @@ def max_abs_dpixel(a: np.ndarray, b: np.ndarray) -> int:
     for sh in (16, 8, 0):
         d = max(d, int(np.max(np.abs(((a >> sh) & 0xFF).astype(np.int32) - ((b >> sh) & 0xFF).astype(np.int32)))))
     return d
+
+
+def dump_outputs(path: str, argb: np.ndarray, height: int, width: int) -> None:
+    """--dump-outputs: the frame the last timed step delivered (what a caller of the timed path
+    receives: height x width ARGB32 words) as DIR/image.npy, float32 [height, width, 4] holding every
+    pixel's A, R, G, B bytes (exact in float32; 33 MB at 1920x1080)."""
+    px = np.ascontiguousarray(argb).view(np.uint32).reshape(-1, width)[:height]
+    chans = np.stack([((px >> sh) & 0xFF) for sh in (24, 16, 8, 0)], axis=-1).astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "image.npy"), chans)
 
 
 def main():
@@ -210,7 +233,9 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    ktimes = r.kernel_times(args.steps)
+    # the library keeps the events of its last KERNEL_TIMES_RING launches: kernel_ms is the mean over
+    # the timed launches it still holds (all of them up to that many steps)
+    ktimes = r.kernel_times(min(args.steps, KERNEL_TIMES_RING))
     k_mean = float(np.mean(ktimes))
 
     t = torch.tensor([elapsed, float(shadow_local), k_mean, float(refl_local)], dtype=torch.float64, device=dev)
@@ -268,15 +293,18 @@ def main():
         }
         if balance:
             res["balance"] = balance
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, img, H, W)
         legs = {}
-        if world == 1 and not c5 and not args.no_legs:
+        if args.full and world == 1 and not c5 and not args.no_legs:
             legs["sync"], sync_img = sync_leg(r, args, rays)
             legs["moving_camera"], mv_img, mv_scene = moving_camera_leg(r, args, pipe, frames, sc, primary)
-        rl = roofline(args.config, world, (legs.get("sync") or {}).get("kernel_ms"), k_max, ms_per_step, primary)
+        rl = roofline(args.config, world, (legs.get("sync") or {}).get("kernel_ms"), k_max, ms_per_step,
+                      primary) if args.full else None
         if rl:
             res["roofline"] = rl
         res.update(legs)
-        if not args.no_check or (world == 1 and not args.no_cpu_baseline):
+        if args.full and (not args.no_check or (world == 1 and not args.no_cpu_baseline)):
             base, dpx, check = cpu_leg(sc, st, img, args.cpu_threads, c5, check=not args.no_check,
                                        baseline=world == 1 and not args.no_cpu_baseline, name=args.config,
                                        extra={"sync": (sc, sync_img), "moving_camera": (mv_scene, mv_img)} if legs else None)
@@ -624,6 +652,8 @@ def dry_run(args, world):
     if rank == 0:
         frame = frames[last].numpy()
         expect = pattern_strip(np.arange(H), W)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, frame, H, W)
         ms = 1e3 * elapsed / max(1, args.steps)
         print(json.dumps({"metric": "dry run: strip layout + gloo all-gather + re-assembly (no rendering)",
                           "value": 0.0, "unit": "Mrays/s", "n_gpus": world, "steps": args.steps,

@@ -32,6 +32,41 @@ def test_bench_self_launch_dry_run(n, balance):
     assert line["dry_run"] is True and line["max_abs_dpixel"] == 0
 
 
+@pytest.mark.gpu
+def test_bench_plain_run_more_steps_than_the_kernel_time_ring(tmp_path):
+    """A plain run times as many steps as --steps asks for, beyond the launches whose events the library keeps
+    (kernel_ms then averages the ones it holds), does none of the --full work and dumps the last frame."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    steps = bench.KERNEL_TIMES_RING + 44
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", "2",
+                        "--dump-outputs", str(tmp_path / "out")], cwd=ROOT, env=env, capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = _json_line(r.stdout)
+    assert line["steps"] == steps and line["ms_per_step"] > 0 and line["kernel_ms"] > 0
+    assert not {"roofline", "sync", "moving_camera", "cpu_baseline", "max_abs_dpixel"} & set(line)
+    a = np.load(tmp_path / "out" / "image.npy")
+    assert a.dtype == np.float32 and a.shape == (1080, 1920, 4) and 0.0 <= a.min() and a.max() <= 255.0
+
+
+def test_dump_outputs_holds_the_frame(tmp_path):
+    """--dump-outputs: image.npy is float32 [H, W, 4] with every pixel's A, R, G, B bytes, from which the
+    ARGB32 frame is recovered exactly; padding rows past the image height are left out."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    H, W = 13, 21
+    argb = np.random.default_rng(5).integers(0, 1 << 32, size=(H + 3, W), dtype=np.uint64).astype(np.uint32)
+    bench.dump_outputs(str(tmp_path / "out"), argb.view(np.int32), H, W)
+    a = np.load(tmp_path / "out" / "image.npy")
+    assert a.dtype == np.float32 and a.shape == (H, W, 4)
+    u = a.astype(np.uint32)
+    assert np.array_equal((u[..., 0] << 24) | (u[..., 1] << 16) | (u[..., 2] << 8) | u[..., 3], argb[:H])
+
+
 def test_roofline_recomputable():
     sys.path.insert(0, ROOT)
     import bench

@@ -2,9 +2,11 @@
 against the reference's own Qt-free headers in /root/reference (triangle.h, materials.h,
 camera.h, mat.h, rendererSettings.h) and this repository's C ABI, and linked with the reference's
 own compiled Triangle / vector / colour / matrix translation units (oracle/_ref, `make -C oracle
-ref`).  The program tests/c/adapter_golden builds the scene from reference types and renders it
-through GpuRenderer.  Compiled here (CPU test, where /root/reference exists); the built program
-travels to the GPU box, which renders reference golden cases through it."""
+ref`).  The program (tests/c/adapter_golden.cpp) builds the scene from reference types and renders
+it through GpuRenderer.  __graft_entry__.build() compiles it, where the reference checkout exists,
+into oracle/_ref/ beside the reference harness: that folder holds everything built from the
+reference, stays out of git and goes with the tree to a GPU machine that has no reference
+checkout, where the GPU test renders reference golden cases through the built program."""
 import os
 import subprocess
 
@@ -17,7 +19,7 @@ from test_c_api import read_image, write_scene
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference/tp2"
 SRC = os.path.join(ROOT, "tests", "c", "adapter_golden.cpp")
-EXE = os.path.join(ROOT, "tests", "c", "adapter_golden")
+EXE = os.path.join(ROOT, "oracle", "_ref", "adapter_golden")
 LIBDIR = os.path.join(ROOT, "raytracercpp_amd")
 REF_OBJ = os.path.join(ROOT, "oracle", "_ref", "obj")
 
@@ -31,7 +33,9 @@ def build_adapter_program(out=EXE):
     for d in ("src", "projets", "projets/scene", "projets/renderer"):
         incs += ["-isystem", os.path.join(REF, d)]   # the reference's headers: its own warnings are not ours
     cmd = (["g++", "-std=gnu++17", "-Wall", "-Wextra", "-Werror", "-O1"] + incs + [SRC] + objs +
-           ["-o", out, "-L", LIBDIR, "-lrt_mi355x", "-Wl,-rpath," + LIBDIR, "-L/opt/rocm/lib",
+           # (the library is found from the program's own place too: the tree may be moved after the build)
+           ["-o", out, "-L", LIBDIR, "-lrt_mi355x", "-Wl,-rpath," + LIBDIR + ":$ORIGIN/../../raytracercpp_amd",
+            "-L/opt/rocm/lib",
             "-Wl,-rpath-link,/opt/rocm/lib", "-lm"])
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
@@ -51,8 +55,8 @@ def test_adapter_renders_golden(tmp_path, name):
     """The reference's types through GpuRenderer give the reference's final image (the
     reference-generated golden of tests/golden)."""
     if not os.path.exists(EXE):
-        pytest.fail("tests/c/adapter_golden not built: __graft_entry__.build() compiles it where /root/reference "
-                    "exists, and the built program travels to the GPU box")
+        pytest.fail("oracle/_ref/adapter_golden not built: __graft_entry__.build() compiles it where the reference "
+                    "checkout exists, and oracle/_ref goes with the tree to the GPU machine")
     c = Case(name)
     scene = str(tmp_path / "scene.bin")
     out = str(tmp_path / "image.bin")

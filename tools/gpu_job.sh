@@ -12,10 +12,10 @@
 # Steps:
 #   suite          pytest -m gpu (the whole GPU suite)
 #   smoke          __graft_entry__.smoke()
-#   bench          bench.py (C4 headline line, CPU baseline and check)
-#   bench_fast     bench.py --no-cpu-baseline (C4, check only)
-#   bench_c5       bench.py --config sphere1m_refl --steps 6 --warmup 2 --no-cpu-baseline
-#   bench_hair     bench.py --config hair1m --no-cpu-baseline
+#   bench          bench.py --full (C4 headline line, legs, roofline, CPU baseline and check)
+#   bench_fast     bench.py --full --no-cpu-baseline (C4, check only)
+#   bench_c5       bench.py --full --config sphere1m_refl --steps 6 --warmup 2 --no-cpu-baseline
+#   bench_hair     bench.py --full --config hair1m --no-cpu-baseline
 #   strips1        tools/strip_scaling.py, one frame in flight, every rank, N = 1 2 4 8
 #   strips3        the same with three frames in flight (and one, for the like-for-like ratio)
 #   strips3b       strips3 with cost-balanced band lists (--balance)
@@ -59,12 +59,12 @@ run_step() {
     case "$step" in
     suite) python -u -m pytest tests -m gpu -x -q --timeout 240 --timeout-method thread ;;
     smoke) python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" ;;
-    bench) python bench.py $BA ;;
-    bench_fast) python bench.py --no-cpu-baseline $BA ;;
-    bench_q2) python bench.py --no-cpu-baseline --no-legs --inflight 2 $BA ;;
-    bench_q4) python bench.py --no-cpu-baseline --no-legs --inflight 4 $BA ;;
-    bench_c5) python bench.py --config sphere1m_refl --steps 6 --warmup 2 --no-cpu-baseline $BA ;;
-    bench_hair) python bench.py --config hair1m --steps 20 --warmup 3 --no-cpu-baseline $BA ;;
+    bench) python bench.py --full $BA ;;
+    bench_fast) python bench.py --full --no-cpu-baseline $BA ;;
+    bench_q2) python bench.py --full --no-cpu-baseline --no-legs --inflight 2 $BA ;;
+    bench_q4) python bench.py --full --no-cpu-baseline --no-legs --inflight 4 $BA ;;
+    bench_c5) python bench.py --full --config sphere1m_refl --steps 6 --warmup 2 --no-cpu-baseline $BA ;;
+    bench_hair) python bench.py --full --config hair1m --steps 20 --warmup 3 --no-cpu-baseline $BA ;;
     strips1) python tools/strip_scaling.py --ranks 1 2 4 8 --steps 40 --all-ranks --inflight 1 ;;
     strips3) python tools/strip_scaling.py --ranks 1 2 4 8 --steps 40 --all-ranks --inflight 1 3 ;;
     strips3b) python tools/strip_scaling.py --ranks 1 2 4 8 --steps 40 --all-ranks --inflight 1 3 --balance ;;

@@ -6,4 +6,4 @@ OUT=$1; shift
 mkdir -p $OUT
 export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --pmc "$@" --output-format csv -d $OUT -o run -- \
-    python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OUT/run.log 2>&1
+    python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $OUT/run.log 2>&1

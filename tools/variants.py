@@ -16,7 +16,7 @@ def build(specs):
 def run(names, extra):
     for name in names:
         env = dict(os.environ, RT_LIB_PATH=os.path.join(VDIR, f"librt_{name}.so"))
-        r = subprocess.run([sys.executable, "bench.py", "--no-cpu-baseline"] + extra, cwd=ROOT, env=env,
+        r = subprocess.run([sys.executable, "bench.py", "--full", "--no-cpu-baseline"] + extra, cwd=ROOT, env=env,
                            capture_output=True, text=True, timeout=600)
         line = [l for l in r.stdout.splitlines() if l.startswith("{")]
         if not line:
