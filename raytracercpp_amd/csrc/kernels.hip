@@ -2148,9 +2148,10 @@ __global__ __launch_bounds__(BLOCK, OCT ? RT_OCC_OCT : PLAIN ? RT_OCC_PLAIN : RT
 //   trace:  every sample's closest-hit query, one lane per sample
 //   pass1:  per frame, in sample order: the samples' hits merged into the shared
 //           reflection_hit_info, shade_lit (normal mapping rewrites the shared
-//           record, as in the reference)               renderer.cpp:286, 1015-1044
-//   shadow: every shaded sample's is_shadowed query, one lane per sample
-//   spawn:  reflective hits become the next level's frames
+//           record, as in the reference); the shaded samples go to the shadow
+//           list                                       renderer.cpp:286, 1015-1044
+//   shadow: every shaded sample's is_shadowed query, one lane per list entry;
+//           reflective hits become the next level's frames
 //   resolve (after the next level): the samples' colours summed in sample order,
 //           (total / sc) * reflection, shade_finish    renderer.cpp:316-337, 594-616
 // Per pixel the results are trace_pixel<true>'s, bit for bit.
@@ -2313,10 +2314,6 @@ __global__ __launch_bounds__(BLOCK) void refl_shadow_keys_kernel(KParams P, cons
     keys[t] = spread10(q[0]) | (spread10(q[1]) << 1) | (spread10(q[2]) << 2);
 }
 
-// The chunk's sample slots (ReflArgs::sample_major): slot = i * nfr + (p - c0), nfr = c1 - c0, the i-th
-// samples of consecutive frames side by side, so that the per-frame passes (pass1, resolve: one lane per
-// frame, its samples in order) read their records coalesced; 0: slot = (p - c0) * stride + i, a frame's
-// samples side by side
 // the frame at sorted position p: the level's sorted copy (ReflArgs::frs, refl_sort_frames_kernel) when
 // there is one, else through the order
 __device__ __forceinline__ const FrameRec& refl_frame(const ReflArgs& A, int p)
@@ -2324,6 +2321,10 @@ __device__ __forceinline__ const FrameRec& refl_frame(const ReflArgs& A, int p)
     return A.frs ? A.frs[p] : A.fr[A.order[p]];
 }
 
+// The chunk's sample slots (ReflArgs::sample_major): slot = i * nfr + (p - c0), nfr = c1 - c0, the i-th
+// samples of consecutive frames side by side, so that the per-frame passes (pass1, resolve: one lane per
+// frame, its samples in order) read their records coalesced; 0: slot = (p - c0) * stride + i, a frame's
+// samples side by side
 __device__ __forceinline__ int slot_pos(const ReflArgs& A, int slot)
 {
     return A.sample_major ? A.c0 + slot % (A.c1 - A.c0) : A.c0 + slot / A.stride;
@@ -2354,92 +2355,36 @@ __device__ __forceinline__ v3 refl_dir(const FrameRec& F, int i)
     return ld3(F.perfect);
 }
 
-// keys of the feed's tickets (ReflArgs::perm, RT_REFL_DIR_SORT): each slot's direction binned by its
-// cube-map face and a 2 x 2 cell of the face (the slots without a ray last); a stable sort by these keys
-// keeps the slots' order (the frames' Morton order) inside each bin, so that a wave's lanes take rays of
-// nearby origins and similar directions
-__global__ __launch_bounds__(BLOCK) void refl_dir_keys_kernel(KParams P, ReflArgs A, uint32_t* keys, int32_t* vals)
-{
-    const int slot = (int)(blockIdx.x * BLOCK + threadIdx.x);
-    const int nslot = (A.c1 - A.c0) * A.stride;
-    if (slot >= nslot)
-        return;
-    const int i = slot_sample(A, slot);
-    const FrameRec& F = refl_frame(A, slot_pos(A, slot));
-    uint32_t key = 127u;
-    if (i < F.nsamp && A.level <= P.max_recursion_depth) {
-        const v3 d = refl_dir(F, i);
-        const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
-        int face;
-        float u, v, m;
-        if (ax >= ay && ax >= az) {
-            face = d.x < 0 ? 1 : 0;
-            u = d.y, v = d.z, m = ax;
-        } else if (ay >= az) {
-            face = d.y < 0 ? 3 : 2;
-            u = d.x, v = d.z, m = ay;
-        } else {
-            face = d.z < 0 ? 5 : 4;
-            u = d.x, v = d.y, m = az;
-        }
-        const uint32_t cu = m > 0 && u > 0 ? 1u : 0u, cv = m > 0 && v > 0 ? 1u : 0u;
-        key = d.x == d.x && d.y == d.y && d.z == d.z ? (uint32_t)face << 2 | cu << 1 | cv : 126u;
-    }
-    keys[slot] = key;
-    vals[slot] = slot;
-}
-
-// keys of the deferred queries (ReflArgs::defer, RT_REFL_DEFER_SORT): each slot's frame position, so that
-// refl_trace_long_kernel takes them in the frames' Morton order (nearby origins in a wave)
-__global__ __launch_bounds__(BLOCK) void refl_defer_keys_kernel(ReflArgs A, int n, uint32_t* keys)
-{
-    int t = blockIdx.x * BLOCK + threadIdx.x;
-    if (t < n)
-        keys[t] = (uint32_t)(slot_pos(A, A.defer[t]) - A.c0);
-}
-
 // gen: one thread per sample slot of the chunk
 // gen + trace: each sample slot's direction (path-keyed RNG: no draw depends on another
-// sample, renderer.cpp:296-315) written to its record, then the sample's closest-hit query.
-// One kernel, so that the record writes overlap the traversals.
+// sample, renderer.cpp:296-315), then the sample's closest-hit query.  The direction and the ray
+// flag go to the sample's 32-B RawHit (written by the trace kernel, coalesced) and nothing to the
+// 72-B record, which only shaded samples fill.
 __device__ __forceinline__ bool refl_gen(const KParams& P, const ReflArgs& A, int slot, v3& dir, unsigned& count)
 {
     const int i = slot_sample(A, slot);
     const FrameRec& F = refl_frame(A, slot_pos(A, slot));
-    SampleRec& S = A.sm[slot];
-    // fused: a sample's direction and ray flag go to its 32-B RawHit (written by the trace
-    // kernel, coalesced) and nothing to the 72-B record, which only shaded samples fill
-    if (i >= F.nsamp) {
-        if (!A.fused) {
-            S.kind = 2;
-            S.ray = 0;
-            S.sh = 0;
-            S.child = -1;
-        }
+    if (i >= F.nsamp)
         return false;
-    }
     dir = refl_dir(F, i);
-    if (!A.fused)
-        st3(S.d, dir);
     if (i == 0)
         count = (unsigned)F.nsamp;   // reflection rays
     if (A.level > P.max_recursion_depth) {   // trace_ray's depth guard (renderer.cpp:1012-1013)
-        if (A.fused) {
-            A.res[slot] = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
-        } else {
-            S.kind = 0;
-            st3(S.fc, col(0.0f, 0.0f, 0.0f));
-            S.ray = 0;
-            S.sh = 0;
-            S.child = -1;
-        }
+        A.res[slot] = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
         return false;
     }
-    if (!A.fused) {
-        S.kind = 1;
-        S.ray = 1;
-    }
     return true;
+}
+
+// a slot without a ray (pass1 skips it: bit 1 clear)
+__device__ __forceinline__ void refl_no_ray(const ReflArgs& A, int slot, v3 dir)
+{
+    RawHit H;
+    H.t = H.u = H.v = 0.0f;
+    H.k = -1;
+    st3(H.d, dir);
+    H.r = 0;
+    A.hit[slot] = H;
 }
 
 #ifndef RT_REFL_G
@@ -2470,14 +2415,8 @@ __global__ __launch_bounds__(BLOCK, RT_OCC_REFL) void refl_trace_kernel(KParams 
     bool ray = slot < nslot && refl_gen(P, A, slot, dir, count);
     wave_count_add(&P.counters[1], lead ? count : 0u);
     if (!ray) {
-        if (A.fused && slot < nslot && lead) {   // no ray (pass1 skips it: bit 1 clear)
-            RawHit H;
-            H.t = H.u = H.v = 0.0f;
-            H.k = -1;
-            st3(H.d, dir);
-            H.r = 0;
-            A.hit[slot] = H;
-        }
+        if (slot < nslot && lead)
+            refl_no_ray(A, slot, dir);
         return;
     }
     refl_trace_one<G>(P, A, slot, dir, lv, (uint32_t)A.max_steps);
@@ -2555,80 +2494,54 @@ struct ReflFeed {
             return;
         }
         st3(H.d, d);
-        H.r = (r ? 1 : 0) | (A->fused ? 2 : 0);
+        H.r = (r ? 1 : 0) | 2;
         A->hit[slot] = H;
     }
 
-    // wave-uniform: the waiting lanes (want) take the next slots; true for a lane given a ray (hi, risk and
-    // rsub stay the call's: INFINITY, none, 0; nob: the origin cones, ocone.hpp)
-    __device__ __forceinline__ bool fetch(bool want, v3& o, v3& d, float& m, float&, const uint64_t*&, float&, bool& nob)
+    // wave-uniform: the waiting lanes (want) take the next slots; true for a lane given a ray (nob: the
+    // origin cones, ocone.hpp)
+    __device__ __forceinline__ bool fetch(bool want, v3& o, v3& d, float& m, bool& nob)
     {
         const uint64_t wb = __ballot(want);
         if (!wb)
             return false;
         const int leader = __ffsll((unsigned long long)wb) - 1;
         const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(wb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)wb, 0u));
-        if (A->feed_parts) {
-            // the slots in eighths, one ticket each: a wave starts on its XCD's eighth (workgroups go to the
-            // 8 XCDs round robin), so that each XCD's L2 holds the nodes of one part of the frames' Morton
-            // order, and moves on to the next eighths when its own is exhausted
-            const int xcd = (int)(blockIdx.x & 7);
-            int base = 0, lim = 0;
-            for (;;) {
-                if (part >= 8) {
-                    drained = true;
-                    return false;
-                }
-                const int x = (xcd + part) & 7;
-                const int lo = (int)((long long)nslot * x / 8), hi = (int)((long long)nslot * (x + 1) / 8);
-                int b = 0;
-                if ((int)(threadIdx.x & 63) == leader)
-                    b = (int)atomicAdd(A->feed_parts + x, (unsigned)__popcll(wb));
-                b = __shfl(b, leader);
-                if (lo + b < hi) {
-                    base = lo + b;
-                    lim = hi;
-                    break;
-                }
-                part++;
+        // the slots in eighths, one ticket each: a wave starts on its XCD's eighth (workgroups go to the
+        // 8 XCDs round robin), so that each XCD's L2 holds the nodes of one part of the frames' Morton
+        // order, and moves on to the next eighths when its own is exhausted
+        const int xcd = (int)(blockIdx.x & 7);
+        int base = 0, lim = 0;
+        for (;;) {
+            if (part >= 8) {
+                drained = true;
+                return false;
             }
-            drained = false;
-            if (!want)
-                return false;
-            slot = base + rank;
-            if (slot >= lim)
-                return false;
-        } else {
-            int base = 0;
+            const int x = (xcd + part) & 7;
+            const int lo = (int)((long long)nslot * x / 8), hi = (int)((long long)nslot * (x + 1) / 8);
+            int b = 0;
             if ((int)(threadIdx.x & 63) == leader)
-                base = (int)atomicAdd(A->feed_ticket, (unsigned)__popcll(wb));
-            base = __shfl(base, leader);
-            drained = base + __popcll(wb) >= nslot;
-            if (!want)
-                return false;
-            slot = base + rank;
-            if (slot >= nslot)
-                return false;
+                b = (int)atomicAdd(A->feed_parts + x, (unsigned)__popcll(wb));
+            b = __shfl(b, leader);
+            if (lo + b < hi) {
+                base = lo + b;
+                lim = hi;
+                break;
+            }
+            part++;
         }
-        // the tickets in frame order (a frame's samples on adjacent lanes: one origin, coherent first
-        // steps), whatever the slots' order
-        if (A->perm)
-            slot = A->perm[slot];
-        else if (A->sample_major && A->feed_frame_order)
-            slot = slot_of(*A, A->c0 + slot / A->stride, slot % A->stride);
+        drained = false;
+        if (!want)
+            return false;
+        slot = base + rank;
+        if (slot >= lim)
+            return false;
         v3 dir = mk(0, 0, 0);
         unsigned c = 0;   // (refl_gen sets it for a frame's first sample: the frame's reflection rays)
         const bool gen = refl_gen(*P, *A, slot, dir, c);
         count += c;
         if (!gen) {
-            if (A->fused) {   // no ray (pass1 skips it: bit 1 clear)
-                RawHit H;
-                H.t = H.u = H.v = 0.0f;
-                H.k = -1;
-                st3(H.d, dir);
-                H.r = 0;
-                A->hit[slot] = H;
-            }
+            refl_no_ray(*A, slot, dir);
             return false;
         }
         const FrameRec& F = refl_frame(*A, slot_pos(*A, slot));
@@ -2678,9 +2591,6 @@ __global__ __launch_bounds__(BLOCK, RT_OCC_FEED) void refl_trace_feed_kernel(KPa
 #endif
 }
 
-#ifndef RT_REFL_LONG_QUEUE
-#define RT_REFL_LONG_QUEUE 1   // refl_trace_long_kernel: waves take batches from a ticket (0: grid stride)
-#endif
 #ifndef RT_REFL_LONG_G
 #define RT_REFL_LONG_G 8   // lanes per deferred reflection query (refl_trace_long_kernel; r06: with lane refill only
                            // the overflowed / uncertified queries come here, the longest: C5 1,105 -> 1,078 ms at 8)
@@ -2699,7 +2609,6 @@ __global__ __launch_bounds__(BLOCK, RT_OCC_REFL) void refl_trace_long_kernel(KPa
     extern __shared__ uint2 lds_levels[];
     uint2* lv = lds_levels + threadIdx.x;
     const int n = (int)ldg(A.defer_count);
-#if RT_REFL_LONG_QUEUE
     // a wave takes the next 64 / G queries from a ticket (defer_count[1], zeroed with the count) when it
     // is done with its last ones: the waves' batches differ in length, a fixed grid stride left the
     // kernel to its slowest wave's sum of batches
@@ -2714,10 +2623,6 @@ __global__ __launch_bounds__(BLOCK, RT_OCC_REFL) void refl_trace_long_kernel(KPa
         const int i = base + lane / G;   // query i: lanes G i .. G i + G - 1 of the batch
         if (i >= n)
             continue;
-#else
-    // query i is held by lanes G i .. G i + G - 1 of the grid (whole groups inside one wave)
-    for (int i = (int)((blockIdx.x * BLOCK + threadIdx.x) / G); i < n; i += (int)(gridDim.x * BLOCK / G)) {
-#endif
         const int slot = A.defer[i];
         unsigned count = 0;
         v3 dir = mk(0, 0, 0);
@@ -2769,7 +2674,7 @@ __device__ __forceinline__ void refl_trace_one(const KParams& P, const ReflArgs&
     H.v = h.v;
     H.k = h.k;
     st3(H.d, dir);
-    H.r = (r ? 1 : 0) | (A.fused ? 2 : 0);
+    H.r = (r ? 1 : 0) | 2;
     if (G == 1 || (threadIdx.x & (G - 1)) == 0)
         A.hit[slot] = H;
 }
@@ -2803,9 +2708,9 @@ __global__ __launch_bounds__(BLOCK, RT_OCC_REFL) void refl_pass1_kernel(KParams 
             int slot = slot_of(A, p, i);
             SampleRec& S = A.sm[slot];
             const RawHit H = A.hit[slot];
-            if (A.fused ? !(H.r & 2) : !S.ray)
+            if (!(H.r & 2))
                 continue;   // depth limit: trace_ray returns before touching the record
-            const v3 d = A.fused ? ld3(H.d) : ld3(S.d);
+            const v3 d = ld3(H.d);
             THit h;
             h.t = H.t;
             h.u = H.u;
@@ -2815,15 +2720,10 @@ __global__ __launch_bounds__(BLOCK, RT_OCC_REFL) void refl_pass1_kernel(KParams 
             int s = -1;
             bvh_record(P, h, (H.r & 1) != 0, local, rhi, s);
             shapes_closest(P, ro, d, local, rhi, s);
-            if (!A.fused) {
-                S.sh = 0;
-                S.child = -1;
-            }
             if (rhi.t > 0.1f) {
                 v3 ip;
                 c3 fc = shade_lit(P, ro, d, rhi, ip);   // may normal-map rhi.normal (persists)
-                if (A.fused)
-                    list_append(A, slot);   // a shaded sample: its shadow query (and spawn)
+                list_append(A, slot);   // a shaded sample: its shadow query (and spawn)
                 S.kind = 1;
                 st3(S.fc, fc);
                 st3(S.ip, ip);
@@ -2836,56 +2736,28 @@ __global__ __launch_bounds__(BLOCK, RT_OCC_REFL) void refl_pass1_kernel(KParams 
             } else {
                 float a;
                 const c3 mc = miss_color(P, d, a);
-                if (A.fused) {
-                    A.res[slot] = make_float4(mc.r, mc.g, mc.b, __int_as_float(-1));
-                } else {
-                    S.kind = 0;
-                    st3(S.fc, mc);
-                }
+                A.res[slot] = make_float4(mc.r, mc.g, mc.b, __int_as_float(-1));
             }
         }
     }
     wave_count_add(&P.counters[0], nshadow);
 }
 
-// list: the shaded samples (the only ones with a shadow query), compacted so that
-// the shadow pass runs on full waves (one atomic per wave)
-__global__ __launch_bounds__(BLOCK) void refl_list_kernel(KParams P, ReflArgs A)
-{
-    int slot = blockIdx.x * BLOCK + threadIdx.x;
-    int nslot = (A.c1 - A.c0) * A.stride;
-    bool need = slot < nslot && A.sm[slot].ray && A.sm[slot].kind == 1;
-    if (slot < nslot && !need)
-        A.sm[slot].sh = 0;
-    uint64_t m = __ballot(need);
-    if (!m)
-        return;
-    uint32_t base = 0;
-    int leader = __ffsll((unsigned long long)m) - 1;
-    if ((threadIdx.x & 63) == leader)
-        base = atomicAdd(A.list_count, (unsigned)__popcll(m));
-    base = __shfl(base, leader);
-    if (need)
-        A.list[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = slot;
-}
-
 __device__ __forceinline__ int spawn_sample(const KParams& P, const ReflArgs& A, int slot, SampleRec& S, bool sh);
 
-// a sample's shadow decided: its record, and (fused) the child frame it spawns and the colour it returns
+// a sample's shadow decided: its record, the child frame it spawns and the colour it returns
 __device__ __forceinline__ void refl_shadow_done(const KParams& P, const ReflArgs& A, int slot, bool sh)
 {
     SampleRec& S = A.sm[slot];
     S.sh = sh ? 1 : 0;
-    if (A.fused) {
-        // the colour this sample returns (resolve, below): its child frame's, or its own finished shade
-        const int child = spawn_sample(P, A, slot, S, sh);
-        c3 c = col(0.0f, 0.0f, 0.0f);
-        if (child < 0) {
-            const float* m = mat_of(P, S.mat);
-            c = shade_finish(P, shade_shadow_emit(P, ldc(S.fc), m, sh), m, col(0, 0, 0));
-        }
-        A.res[slot] = make_float4(c.r, c.g, c.b, __int_as_float(child));
+    // the colour this sample returns (resolve, below): its child frame's, or its own finished shade
+    const int child = spawn_sample(P, A, slot, S, sh);
+    c3 c = col(0.0f, 0.0f, 0.0f);
+    if (child < 0) {
+        const float* m = mat_of(P, S.mat);
+        c = shade_finish(P, shade_shadow_emit(P, ldc(S.fc), m, sh), m, col(0, 0, 0));
     }
+    A.res[slot] = make_float4(c.r, c.g, c.b, __int_as_float(child));
 }
 
 // shadow: is_shadowed (renderer.cpp:340-402) for every shaded sample (via the list)
@@ -2903,127 +2775,12 @@ __global__ __launch_bounds__(BLOCK, RT_OCC_REFL) void refl_shadow_kernel(KParams
     unsigned t = blockIdx.x * BLOCK + threadIdx.x;
     if (t >= *A.list_count)
         return;
-    const int slot = A.list[t];
-    SampleRec& S = A.sm[slot];
+    const SampleRec& S = A.sm[A.list[t]];
     v3 light = mk(P.light[0], P.light[1], P.light[2]);
-    refl_shadow_done(P, A, slot, is_shadowed<false, 1, RT_REFL_SHADOW_CALL != 0>(P, ld3(S.ip), ld3(S.nrm), light, lv));
-}
-
-// Lane refill for the shadow pass (ReflArgs::shadow_feed; the reflection queries' ReflFeed, above): most
-// shadow segments end in a few steps and a few run long (lane utilisation ~0.2 with one segment per
-// lane).  Per list entry the query is is_shadowed's wide part (wide_shadow: the segment [0, hi], no ties,
-// the light's risk words when they hold for the ray) and the decision its; the entries it does not decide
-// (a stack overflow, an uncertified hit, a NaN ray, no segment query) go to the deferred list, which
-// refl_shadow_kernel runs as before (deep retry, octree segment query).  Each entry's result is
-// refl_shadow_kernel's, bit for bit.
-struct ShadowFeed {
-    static constexpr bool on = true;
-    bool busy = false;
-    bool drained = false;
-    int threshold;
-    int slot = -1;
-    const KParams* P;
-    const ReflArgs* A;
-    int nlist;
-    v3 light;
-
-    __device__ __forceinline__ void defer() const
-    {
-        const uint64_t mk = __ballot(1);
-        const int leader = __ffsll((unsigned long long)mk) - 1;
-        uint32_t base = 0;
-        if ((int)(threadIdx.x & 63) == leader)
-            base = atomicAdd(A->sdefer_count, (unsigned)__popcll(mk));
-        base = __shfl(base, leader);
-        A->sdefer[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u))] = slot;
-    }
-
-    __device__ __forceinline__ void finish(int st, WHit& w, v3 o, v3 d)
-    {
-        busy = false;
-        bool sh = false;
-        if (st == W_HIT) {
-            // wide_shadow: a certified minimum hit t* <= hi is the reference's record t
-            if (!kdop_certifies(load_gnode(P->nodes + ldg(P->wmeta + w.k).y), o, d, w.t)) {
-                defer();
-                return;
-            }
-            const v3 p = ld3(A->sm[slot].ip);
-            const v3 q = o + d * w.t;
-            sh = length2(p - q) < length2(p - light);
-        } else if (st != W_MISS) {   // (a miss: lit)
-            defer();
-            return;
-        }
-        refl_shadow_done(*P, *A, slot, sh);
-    }
-
-    __device__ __forceinline__ bool fetch(bool want, v3& o, v3& d, float& m, float& hi, const uint64_t*& risk, float& rsub,
-                                          bool&)
-    {
-        const uint64_t wb = __ballot(want);
-        if (!wb)
-            return false;
-        const int leader = __ffsll((unsigned long long)wb) - 1;
-        int base = 0;
-        if ((int)(threadIdx.x & 63) == leader)
-            base = (int)atomicAdd(A->shadow_ticket, (unsigned)__popcll(wb));
-        base = __shfl(base, leader);
-        drained = base + __popcll(wb) >= nlist;
-        if (!want)
-            return false;
-        const int t = base + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(wb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)wb, 0u));
-        if (t >= nlist)
-            return false;
-        slot = A->list[t];
-        if (!P->compute_shadows) {   // (is_shadowed: lit)
-            refl_shadow_done(*P, *A, slot, false);
-            return false;
-        }
-        const SampleRec& S = A->sm[slot];
-        const v3 p = ld3(S.ip), n = ld3(S.nrm);
-        o = p + n * 1.0e-4f;
-        d = normalize(light - p);
-        if (!(P->enable_bvh && P->seg_scale > 0.0f && P->wnodes && P->nnodes > 0)) {
-            defer();
-            return false;
-        }
-        // is_shadowed's segment end and risk words, the same expressions
-        const TRay R0 = make_ray(*P, o, d);
-        const float ms = seg_margin(*P, R0);
-        const float nl = fabsf(n.x) + fabsf(n.y) + fabsf(n.z);
-        hi = (sqrtf(length2(p - light)) + 1.0e-4f * nl) * (1.0f + 0x1p-10f) + ms;
-        if (R0.nan) {
-            defer();
-            return false;
-        }
-        const bool lr = P->wrisk && hi <= P->risk_G && nl <= P->risk_nl;
-        risk = lr ? P->wrisk : nullptr;
-        rsub = lr ? wrisk_sub(W_QS_SHADOW, hi, P->risk_nu) : 0.0f;
-        const float om = fmaxf(fabsf(o.x), fmaxf(fabsf(o.y), fabsf(o.z)));
-        m = 0x1p-16f * (om + P->scene_scale);
-        busy = true;
-        return true;
-    }
-};
-
-__global__ __launch_bounds__(BLOCK, RT_OCC_REFL) void refl_shadow_feed_kernel(KParams P_arg, ReflArgs A)
-{
-    const KParams& P = kernel_params();
-    (void)P_arg;
-    extern __shared__ uint2 lds_levels[];
-    uint2* lv = lds_levels + threadIdx.x;
-    ShadowFeed feed;
-    feed.threshold = A.shadow_feed;
-    feed.P = &P;
-    feed.A = &A;
-    feed.nlist = (int)*A.list_count;
-    feed.light = mk(P.light[0], P.light[1], P.light[2]);
-    WStackLdsN<W_STACK_REFL_FEED> stk{lv};
-    WHit w;
-    wbvh_closest<WStackLdsN<W_STACK_REFL_FEED>, 1, ShadowFeed>(P.wnodes, P.wtris, mk(0, 0, 0), mk(1, 0, 0), 0.0f, stk, w,
-                                                               nullptr, INFINITY, false, W_QS_SHADOW, nullptr, 1, 0.0f, 0u,
-                                                               &feed);
+    const bool sh = is_shadowed<false, 1, RT_REFL_SHADOW_CALL != 0>(P, ld3(S.ip), ld3(S.nrm), light, lv);
+    // the slot read again (the list is not written here): held across the query's calls it cost 2 more
+    // spilled VGPRs, 888 against 872 B of scratch (ROCm 7.2, clang 22)
+    refl_shadow_done(P, A, A.list[t], sh);
 }
 
 // a shaded sample with a reflective material becomes a frame of the next level (its
@@ -3037,28 +2794,10 @@ __device__ __forceinline__ int spawn_sample(const KParams& P, const ReflArgs& A,
     const FrameRec& F = refl_frame(A, slot_pos(A, slot));
     unsigned idx = atomicAdd(A.child_count, 1u);
     c3 dfc = shade_shadow_emit(P, ldc(S.fc), m, sh);
-    make_frame(P, A.child_fr[idx], ld3(S.ip), ld3(S.nrm), A.fused ? ld3(A.hit[slot].d) : ld3(S.d), dfc, S.crough, S.mat,
+    make_frame(P, A.child_fr[idx], ld3(S.ip), ld3(S.nrm), ld3(A.hit[slot].d), dfc, S.crough, S.mat,
                child_key(F.key, (uint32_t)i), -1);
     S.child = (int)idx;
     return (int)idx;
-}
-
-// spawn: reflective hits become frames of the next level (A.fused == 0; else the shadow pass)
-__global__ __launch_bounds__(BLOCK) void refl_spawn_kernel(KParams P_arg, ReflArgs A)
-{
-    // the parameters where the kernel received them (not a copy: passing the by-value argument to a
-    // call made every lane copy it to scratch, r05: C5's shadow pass wrote ~90 GB per launch)
-    const KParams& P = kernel_params();
-    (void)P_arg;
-    int slot = blockIdx.x * BLOCK + threadIdx.x;
-    int nslot = (A.c1 - A.c0) * A.stride;
-    if (slot >= nslot)
-        return;
-    SampleRec& S = A.sm[slot];
-    S.child = -1;
-    if (!S.ray || S.kind != 1)
-        return;
-    spawn_sample(P, A, slot, S, S.sh != 0);
 }
 
 // resolve: compute_reflection's sum in sample order, then the frame's hit colour
@@ -3076,24 +2815,9 @@ __global__ __launch_bounds__(BLOCK) void refl_resolve_kernel(KParams P_arg, Refl
     c3 total = col(0.0f, 0.0f, 0.0f);
     for (int i = 0; i < F.nsamp; i++) {
         const int slot = slot_of(A, p, i);
-        c3 ret;
-        if (A.fused) {   // 16 B per sample instead of its 72-B record
-            const float4 r = A.res[slot];
-            const int child = __float_as_int(r.w);
-            ret = child >= 0 ? ldc(A.child_ret + 3 * (size_t)child) : col(r.x, r.y, r.z);
-            total = total + ret;
-            continue;
-        }
-        const SampleRec& S = A.sm[slot];
-        if (S.kind == 0)
-            ret = ldc(S.fc);
-        else if (S.child >= 0)
-            ret = ldc(A.child_ret + 3 * (size_t)S.child);
-        else {
-            const float* m = mat_of(P, S.mat);
-            ret = shade_finish(P, shade_shadow_emit(P, ldc(S.fc), m, S.sh != 0), m, col(0, 0, 0));
-        }
-        total = total + ret;
+        const float4 r = A.res[slot];   // 16 B per sample instead of its 72-B record
+        const int child = __float_as_int(r.w);
+        total = total + (child >= 0 ? ldc(A.child_ret + 3 * (size_t)child) : col(r.x, r.y, r.z));
     }
     const float* m = mat_of(P, F.mat);
     float sc = (float)F.nsamp, rf = m[12];
@@ -4320,7 +4044,7 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_refl_level
     return hipGetLastError();
 }
 
-// stage: 1 gen + trace, 2 pass1, 3 shadow, 4 spawn, 5 resolve, 6 list, 7 the deferred long traces
+// stage: 1 gen + trace, 7 the deferred long traces, 2 pass1 (+ shadow list), 3 shadow (+ spawn), 5 resolve
 extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_refl_stage(int stage, const rt::KParams* P,
                                                                           const rt::ReflArgs* A, hipStream_t stream)
 {
@@ -4343,22 +4067,7 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_refl_stage
     case 7: hipLaunchKernelGGL(rt::refl_trace_long_kernel, dim3(std::min<unsigned>(gs.x, 2048u)), dim3(rt::BLOCK), lds,
                                stream, *P, *A); break;
     case 2: hipLaunchKernelGGL(rt::refl_pass1_kernel, gf, dim3(rt::BLOCK), 0, stream, *P, *A); break;
-    case 3:
-        if (A->shadow_feed > 0 && A->fused && !RT_COUNT) {
-            // persistent waves (lane refill), then the entries they deferred by the one-query kernel
-            hipLaunchKernelGGL(rt::refl_shadow_feed_kernel,
-                               dim3(std::max(1u, std::min<unsigned>(gs.x, (unsigned)(P->max_blocks / 8 * RT_OCC_REFL)))),
-                               dim3(rt::BLOCK), (size_t)std::max(P->levels, rt::W_STACK_REFL_FEED) * rt::BLOCK * sizeof(uint2),
-                               stream, *P, *A);
-            rt::ReflArgs D = *A;
-            D.list = A->sdefer;
-            D.list_count = A->sdefer_count;
-            hipLaunchKernelGGL(rt::refl_shadow_kernel, gs, dim3(rt::BLOCK), lds, stream, *P, D);
-        } else
-            hipLaunchKernelGGL(rt::refl_shadow_kernel, gs, dim3(rt::BLOCK), lds, stream, *P, *A);
-        break;
-    case 4: hipLaunchKernelGGL(rt::refl_spawn_kernel, gs, dim3(rt::BLOCK), 0, stream, *P, *A); break;
-    case 6: hipLaunchKernelGGL(rt::refl_list_kernel, gs, dim3(rt::BLOCK), 0, stream, *P, *A); break;
+    case 3: hipLaunchKernelGGL(rt::refl_shadow_kernel, gs, dim3(rt::BLOCK), lds, stream, *P, *A); break;
     default: hipLaunchKernelGGL(rt::refl_resolve_kernel, gf, dim3(rt::BLOCK), 0, stream, *P, *A); break;
     }
     return hipGetLastError();
@@ -4391,25 +4100,6 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_refl_shado
     if (n > 0)
         hipLaunchKernelGGL(rt::refl_shadow_keys_kernel, dim3((n + rt::BLOCK - 1) / rt::BLOCK), dim3(rt::BLOCK), 0, stream, *P,
                            sm, list, n, keys);
-    return hipGetLastError();
-}
-
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_refl_dir_keys(const rt::KParams* P, const rt::ReflArgs* A,
-                                                                              uint32_t* keys, int32_t* vals, hipStream_t stream)
-{
-    const int n = (A->c1 - A->c0) * A->stride;
-    if (n > 0)
-        hipLaunchKernelGGL(rt::refl_dir_keys_kernel, dim3((n + rt::BLOCK - 1) / rt::BLOCK), dim3(rt::BLOCK), 0, stream, *P,
-                           *A, keys, vals);
-    return hipGetLastError();
-}
-
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_refl_defer_keys(const rt::ReflArgs* A, int n, uint32_t* keys,
-                                                                                hipStream_t stream)
-{
-    if (n > 0)
-        hipLaunchKernelGGL(rt::refl_defer_keys_kernel, dim3((n + rt::BLOCK - 1) / rt::BLOCK), dim3(rt::BLOCK), 0, stream, *A, n,
-                           keys);
     return hipGetLastError();
 }
 

@@ -199,30 +199,32 @@ struct FrameRec {
     int32_t parent;     // launch-local pixel (level 1 frames)
 };
 
-// One sample of a frame: trace_ray(depth + 1) into the frame's shared HitInfo.
+// One shaded sample of a frame: trace_ray(depth + 1) into the frame's shared HitInfo.  Only the samples
+// that pass1 shades fill their record (the others' results are in RawHit and ReflArgs::res); d and ray
+// are not used (the direction and the ray flag are RawHit's) and keep the record's 72-B layout.
 struct SampleRec {
-    float d[3];         // direction
-    int32_t kind;       // 0: colour final in fc (miss / depth limit), 1: shaded hit, 2: no sample
-    float fc[3];        // shade_lit colour (kind 1) or the returned colour (kind 0)
+    float d[3];
+    int32_t kind;       // 1: shaded hit
+    float fc[3];        // shade_lit colour
     float ip[3];        // hit point
     float nrm[3];       // shading normal after normal mapping
     int32_t mat;
     float crough;       // roughness of the frame this hit spawns (reflective material)
     int32_t sh;         // is_shadowed
     int32_t child;      // frame index at the next level
-    int32_t ray;        // 1: closest-hit query to trace
+    int32_t ray;
 };
 
 struct RawHit {
     float t, u, v;
     int32_t k;          // GTri slot, -1 none
-    float d[3];         // the sample's direction (ReflArgs::fused; else in SampleRec::d)
-    int32_t r;          // bit 0: the query's return value; bit 1 (fused): the sample traced a ray
+    float d[3];         // the sample's direction
+    int32_t r;          // bit 0: the query's return value; bit 1: the sample traced a ray
 };
 
 struct ReflArgs {
     FrameRec* fr;            // this level's frames
-    SampleRec* sm;           // the chunk's samples, (p - c0) * stride + i for sorted position p
+    SampleRec* sm;           // the chunk's samples, by slot (kernels.hip slot_of)
     RawHit* hit;             // per sample
     float* ret;              // per frame of this level: colour returned to the parent sample (3 floats)
     const float* child_ret;  // the next level's ret
@@ -230,35 +232,22 @@ struct ReflArgs {
     unsigned int* child_count;
     const int32_t* order;    // frame at sorted position p is order[p] (spatially sorted)
     const FrameRec* frs;     // (optional) the frames copied in sorted order: frs[p] = fr[order[p]]
-    const int32_t* perm;     // (optional) the feed's ticket t takes slot perm[t] (slots grouped by direction)
-    unsigned int* feed_parts;   // (optional) 8 tickets, one per eighth of the slots: a wave takes its XCD's
-                                // eighth first, then the next ones (RT_REFL_FEED_XCD)
-    int32_t* list;           // compacted sample slots with a shadow query
+    unsigned int* feed_parts;   // the feed's 8 tickets, one per eighth of the slots: a wave takes its XCD's
+                                // eighth first, then the next ones
+    int32_t* list;           // compacted sample slots with a shadow query (pass1 appends them)
     unsigned int* list_count;
     int32_t c0, c1;          // sorted positions [c0, c1) of this level
     int32_t level;           // samples trace at depth = level
     int32_t stride;          // max(N, 1)
     int32_t sample_major;    // the slots' order (kernels.hip slot_of): 1 sample-major, 0 frame-major
-    int32_t feed_frame_order;   // (sample-major) the feed hands out a frame's samples together
-    int32_t fused;           // 1: pass1 builds the shadow list and the shadow pass spawns (no list /
-                             // spawn kernels), and every sample's result is in res; 0: the separate
-                             // passes (RT_REFL_FUSE=0), resolve reads the records
-    float4* res;             // fused: per sample slot, the colour it returns (xyz) or, in w as int bits,
+    float4* res;             // per sample slot, the colour it returns (xyz) or, in w as int bits,
                              // the index of the child frame whose colour it returns (-1: xyz)
     int32_t* defer;          // sample slots whose query ran past max_steps in refl_trace_kernel (traced
     unsigned int* defer_count;   // again by refl_trace_long_kernel, whole waves of long queries); 0: off
     int32_t max_steps;
     // > 0: refl_trace_feed_kernel instead of refl_trace_kernel (persistent waves, lane refill when this
-    // many lanes wait; the queries the wide BVH does not certify go to the defer list); feed_ticket: its
-    // next slot
+    // many lanes wait; the queries the wide BVH does not certify go to the defer list)
     int32_t feed;
-    unsigned int* feed_ticket;
-    // > 0 (fused only): the shadow pass by refl_shadow_feed_kernel (lane refill at this many waiting lanes;
-    // shadow_ticket its next list entry), then refl_shadow_kernel over the entries it deferred (sdefer)
-    int32_t shadow_feed;
-    unsigned int* shadow_ticket;
-    int32_t* sdefer;
-    unsigned int* sdefer_count;
 };
 
 // ---- hybrid rasterisation (kernels.hip "Renderer::raster_trace") ----

@@ -59,10 +59,6 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_ocone(cons
                                                                      const int32_t dim[3], double h, double r, double slack,
                                                                      double QS, double cos_cap, uint2* cells,
                                                                      size_t ncells, hipStream_t stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_refl_defer_keys(const rt::ReflArgs* A, int n, uint32_t* keys,
-                                                                                hipStream_t stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_refl_dir_keys(const rt::KParams* P, const rt::ReflArgs* A,
-                                                                              uint32_t* keys, int32_t* vals, hipStream_t stream);
 extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_refl_shadow_keys(const rt::KParams* P, const rt::SampleRec* sm,
                                                                                  const int32_t* list, int n, uint32_t* keys,
                                                                                  hipStream_t stream);
@@ -126,8 +122,6 @@ Knobs Knobs::from_env()
     k.quick_wbvh = on("RT_WBVH_QUICK_FIRST", true);
     k.fused_ssaa = on("RT_FUSED_SSAA", true);
     k.refl_engine = on("RT_REFL_ENGINE", true);
-    k.refl_sort = on("RT_REFL_SORT", true);
-    k.refl_fuse = on("RT_REFL_FUSE", true);
     k.debug_waves = getenv("RT_DEBUG_WAVES") != nullptr;
     k.exact = on("RT_EXACT", false);
     k.risk = on("RT_WBVH_RISK", true);
@@ -148,16 +142,8 @@ Knobs Knobs::from_env()
         k.refl_defer = std::max(0, atoi(v));
     if (const char* v = getenv("RT_REFL_FEED"))    // lane refill of the reflection queries at this many waiting lanes
         k.refl_feed = std::min(64, std::max(0, atoi(v)));
-    if (const char* v = getenv("RT_REFL_FEED_FRAME_ORDER"))
-        k.refl_feed_frame_order = atoi(v) != 0;
     if (const char* v = getenv("RT_REFL_SAMPLE_MAJOR"))
         k.refl_sample_major = atoi(v) != 0;
-    if (const char* v = getenv("RT_REFL_DIR_SORT"))
-        k.refl_dir_sort = atoi(v) != 0;
-    if (const char* v = getenv("RT_REFL_FEED_XCD"))
-        k.refl_feed_xcd = atoi(v) != 0;
-    if (const char* v = getenv("RT_REFL_DEFER_SORT"))
-        k.refl_defer_sort = atoi(v) != 0;
     if (const char* v = getenv("RT_REFL_SHADOW_SORT"))
         k.refl_shadow_sort = atoi(v) != 0;
     if (const char* v = getenv("RT_REFL_SORTED_FRAMES"))
@@ -168,8 +154,6 @@ Knobs Knobs::from_env()
         k.ocone = atoi(v) != 0;
     if (const char* v = getenv("RT_OCONE_DIM"))
         k.ocone_dim = std::min(1024, std::max(1, atoi(v)));
-    if (const char* v = getenv("RT_REFL_SHADOW_FEED"))
-        k.refl_shadow_feed = std::min(64, std::max(0, atoi(v)));
     {
         const char* v = getenv("RT_INJECT_FRAME_FAIL");   // tests: the k-th ray_trace fails after its image start
         k.inject_fail = v ? std::atoi(v) : 0;
@@ -1252,7 +1236,7 @@ int Renderer::launch_trace(const KParams& P, hipStream_t stream)
     }
     for (auto& L : refl_)
         L.fr.device = L.ret.device = L.sm.device = L.hit.device = L.cnt.device = L.list.device = L.sort.device =
-            L.sort_tmp.device = L.res.device = L.sdefer.device = L.frs.device = L.slist.device = device_;
+            L.sort_tmp.device = L.res.device = L.frs.device = L.slist.device = device_;
     size_t npx = (size_t)P.rw * P.local_rows;
     ReflLevel& L1 = refl_[1];
     if ((e = L1.fr.reserve(npx * sizeof(FrameRec))) != hipSuccess || (e = L1.cnt.reserve(64)) != hipSuccess)
@@ -1281,19 +1265,18 @@ int Renderer::refl_level(const KParams& P, int level, int nframes, hipStream_t s
     hipError_t e;
     // about 2^RT_REFL_CHUNK_LOG2 sample slots per chunk (default 2^27: C5 1,757 / 1,841 / 1,902 / 1,927
     // Mrays/s at 2^24 / 2^25 / 2^26 / 2^27, r05; r02: 0.765 / 0.714 / 0.695 / 0.679 s at 2^21 / 2^23 /
-    // 2^24 / 2^25): one host round trip per chunk, ~204 B of records per
-    // slot (72-B SampleRec, 32-B RawHit, 16-B result, list entry, child frame and its colour).
+    // 2^24 / 2^25): one host round trip per chunk, 220 B of records per
+    // slot (72-B SampleRec, 32-B RawHit, 16-B result, list entry and its sort's 16 B, child frame and its colour).
     // A level may take at most a quarter of the memory still free (what it already holds
     // counts as free), so that the deeper levels, each bounded the same way, fit behind it;
     // an allocation that fails anyway halves the chunk and retries.
-    constexpr size_t SLOT_BYTES = sizeof(SampleRec) + sizeof(RawHit) + 4 + 4 + 16 + sizeof(FrameRec) + 12 + 16;
+    constexpr size_t SLOT_BYTES = sizeof(SampleRec) + sizeof(RawHit) + 4 + 16 + sizeof(FrameRec) + 12 + 16;
     size_t chunk = (size_t)std::max(1024, (1 << knobs_.refl_chunk_log2) / stride);
     {
         size_t freeb = 0, totalb = 0;
         if (hipMemGetInfo(&freeb, &totalb) == hipSuccess) {
             const size_t held =
-                L.sm.bytes + L.hit.bytes + L.list.bytes + L.sdefer.bytes + L.res.bytes + L.frs.bytes + L.slist.bytes + C.fr.bytes +
-                C.ret.bytes;
+                L.sm.bytes + L.hit.bytes + L.list.bytes + L.res.bytes + L.frs.bytes + L.slist.bytes + C.fr.bytes + C.ret.bytes;
             const size_t cap = (freeb + held) / 4 / (SLOT_BYTES * (size_t)stride);
             chunk = std::max<size_t>(1024, std::min(chunk, cap));
         }
@@ -1304,10 +1287,9 @@ int Renderer::refl_level(const KParams& P, int level, int nframes, hipStream_t s
         const size_t slots = std::min((size_t)nframes, chunk) * stride;
         if ((e = L.sm.reserve(slots * sizeof(SampleRec))) == hipSuccess &&
             (e = L.hit.reserve(slots * sizeof(RawHit))) == hipSuccess && (e = L.list.reserve(slots * 4)) == hipSuccess &&
-            (e = L.sdefer.reserve(slots * 4)) == hipSuccess && (e = L.res.reserve(slots * 16)) == hipSuccess &&
-            (e = C.fr.reserve(slots * sizeof(FrameRec))) == hipSuccess &&
+            (e = L.res.reserve(slots * 16)) == hipSuccess && (e = C.fr.reserve(slots * sizeof(FrameRec))) == hipSuccess &&
             (e = C.ret.reserve(slots * 12)) == hipSuccess &&
-            (!(knobs_.refl_shadow_sort || knobs_.refl_dir_sort || knobs_.refl_defer_sort) || (e = L.slist.reserve(slots * 16)) == hipSuccess))
+            (!knobs_.refl_shadow_sort || (e = L.slist.reserve(slots * 16)) == hipSuccess))
             break;
         if (e != hipErrorOutOfMemory || chunk <= 1024)
             return hip_fail(e, "hipMalloc (reflection level)");
@@ -1323,8 +1305,7 @@ int Renderer::refl_level(const KParams& P, int level, int nframes, hipStream_t s
     int32_t* idx_out = idx_in + nframes;
     if ((e = rt_launch_refl_keys(&P, L.fr.as<FrameRec>(), nframes, keys_in, idx_in, stream)) != hipSuccess)
         return hip_fail(e, "refl_keys_kernel launch");
-    const int32_t* order = idx_in;
-    if (knobs_.refl_sort) {
+    {
         size_t tb = 0;
         if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys_in, keys_out, idx_in, idx_out, nframes, 0, 30,
                                                     stream)) != hipSuccess ||
@@ -1332,8 +1313,8 @@ int Renderer::refl_level(const KParams& P, int level, int nframes, hipStream_t s
             (e = hipcub::DeviceRadixSort::SortPairs(L.sort_tmp.p, tb, keys_in, keys_out, idx_in, idx_out, nframes, 0,
                                                     30, stream)) != hipSuccess)
             return hip_fail(e, "frame sort");
-        order = idx_out;
     }
+    const int32_t* order = idx_out;
     // the frames in sorted order, copied once per level (the passes below walk the sorted positions)
     const FrameRec* frs = nullptr;
     if (knobs_.refl_sorted_frames) {
@@ -1346,8 +1327,7 @@ int Renderer::refl_level(const KParams& P, int level, int nframes, hipStream_t s
         ReflArgs A;
         A.order = order;
         A.frs = frs;
-        A.perm = nullptr;
-        A.feed_parts = knobs_.refl_feed_xcd ? L.cnt.as<unsigned int>() + 8 : nullptr;
+        A.feed_parts = L.cnt.as<unsigned int>() + 8;   // (words 8..15 of the 64 B zeroed below)
         A.fr = L.fr.as<FrameRec>();
         A.sm = L.sm.as<SampleRec>();
         A.hit = L.hit.as<RawHit>();
@@ -1363,7 +1343,6 @@ int Renderer::refl_level(const KParams& P, int level, int nframes, hipStream_t s
         A.level = level;
         A.stride = stride;
         A.sample_major = knobs_.refl_sample_major ? 1 : 0;
-        A.feed_frame_order = knobs_.refl_feed_frame_order ? 1 : 0;
         // long queries (more than max_steps loop iterations) leave the trace kernel's waves and are
         // traced again by stage 7 in waves of their own (the shadow list's buffer, free until pass1;
         // RT_REFL_DEFER=0: off)
@@ -1372,64 +1351,12 @@ int Renderer::refl_level(const KParams& P, int level, int nframes, hipStream_t s
         A.max_steps = knobs_.refl_defer;
         // lane refill (kernels.hip refl_trace_feed_kernel; RT_REFL_FEED=k: refill at k waiting lanes, 0: off)
         A.feed = knobs_.refl_feed;
-        A.feed_ticket = L.cnt.as<unsigned int>() + 4;
-        // the shadow pass's lane refill (refl_shadow_feed_kernel; RT_REFL_SHADOW_FEED=k, 0: off)
-        A.shadow_feed = knobs_.refl_shadow_feed;
-        A.shadow_ticket = L.cnt.as<unsigned int>() + 5;
-        A.sdefer = L.sdefer.as<int32_t>();
-        A.sdefer_count = L.cnt.as<unsigned int>() + 6;
-        if ((e = hipMemsetAsync(L.cnt.p, 0, 64, stream)) != hipSuccess)   // (+ the long kernel's and the feeds' counters)
+        if ((e = hipMemsetAsync(L.cnt.p, 0, 64, stream)) != hipSuccess)   // (+ the long kernel's and the feed's counters)
             return hip_fail(e, "hipMemsetAsync");
-        // fused (default): trace, pass1 (+ shadow list), shadow (+ spawn); RT_REFL_FUSE=0: trace,
-        // pass1, list, shadow, spawn
-        A.fused = knobs_.refl_fuse;
-        static const int fused_stages[] = {1, 7, 2, 3}, split_stages[] = {1, 7, 2, 6, 3, 4};
-        const int* st = A.fused ? fused_stages : split_stages;
-        const int nst = A.fused ? 4 : 6;
-        if (knobs_.refl_dir_sort && A.fused && A.feed > 0) {
-            // the feed's tickets over the slots grouped by direction bin (a stable sort: the frames' order
-            // inside each bin); the buffer is free again once the feed is done (the shadow sort reuses it)
-            const int n = (A.c1 - A.c0) * A.stride;
-            uint32_t* kin = L.slist.as<uint32_t>();
-            uint32_t* kout = kin + n;
-            int32_t* vin = reinterpret_cast<int32_t*>(kout + n);
-            int32_t* vout = vin + n;
-            size_t tb = 0;
-            if ((e = rt_launch_refl_dir_keys(&P, &A, kin, vin, stream)) != hipSuccess ||
-                (e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, n, 0, 7, stream)) != hipSuccess ||
-                (e = L.sort_tmp.reserve(tb)) != hipSuccess ||
-                (e = hipcub::DeviceRadixSort::SortPairs(L.sort_tmp.p, tb, kin, kout, vin, vout, n, 0, 7, stream)) !=
-                    hipSuccess)
-                return hip_fail(e, "feed direction sort");
-            A.perm = vout;
-        }
-        for (int k = 0; k < nst; k++) {
-            if (st[k] == 7 && knobs_.refl_defer_sort) {
-                // the deferred queries in their frames' (Morton) order: a wave's lane groups start from nearby
-                // origins (each query's result does not depend on its place in the list)
-                unsigned n = 0;
-                if ((e = hipMemcpyAsync(&n, A.defer_count, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-                    (e = hipStreamSynchronize(stream)) != hipSuccess)
-                    return hip_fail(e, "deferred query count");
-                if (n > 1) {
-                    int bits = 1;
-                    while (bits < 31 && (1u << bits) < (unsigned)(A.c1 - A.c0))
-                        bits++;
-                    uint32_t* kin = L.slist.as<uint32_t>();
-                    uint32_t* kout = kin + n;
-                    int32_t* vout = reinterpret_cast<int32_t*>(kout + n);
-                    size_t tb = 0;
-                    if ((e = rt_launch_refl_defer_keys(&A, (int)n, kin, stream)) != hipSuccess ||
-                        (e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, A.defer, vout, (int)n, 0, bits,
-                                                                stream)) != hipSuccess ||
-                        (e = L.sort_tmp.reserve(tb)) != hipSuccess ||
-                        (e = hipcub::DeviceRadixSort::SortPairs(L.sort_tmp.p, tb, kin, kout, A.defer, vout, (int)n, 0, bits,
-                                                                stream)) != hipSuccess)
-                        return hip_fail(e, "deferred query sort");
-                    A.defer = vout;
-                }
-            }
-            if (st[k] == 3 && A.fused && knobs_.refl_shadow_sort && P.compute_shadows) {
+        // trace, the deferred long traces, pass1 (+ shadow list), shadow (+ spawn)
+        static const int stages[] = {1, 7, 2, 3};
+        for (int st : stages) {
+            if (st == 3 && knobs_.refl_shadow_sort && P.compute_shadows) {
                 // the shadow list sorted by hit point (Morton order): the shadow pass's adjacent lanes start
                 // from nearby points (its entries' results do not depend on their order)
                 unsigned n = 0;
@@ -1451,7 +1378,7 @@ int Renderer::refl_level(const KParams& P, int level, int nframes, hipStream_t s
                     A.list = vout;
                 }
             }
-            if ((e = rt_launch_refl_stage(st[k], &P, &A, stream)) != hipSuccess)
+            if ((e = rt_launch_refl_stage(st, &P, &A, stream)) != hipSuccess)
                 return hip_fail(e, "reflection stage launch");
         }
         unsigned nchild = 0;
@@ -1532,7 +1459,7 @@ int Renderer::launch_raster(const KParams& P, hipStream_t stream)
     PS.tri_uv = A.piece_uv;
     for (auto& L : refl_)
         L.fr.device = L.ret.device = L.sm.device = L.hit.device = L.cnt.device = L.list.device = L.sort.device =
-            L.sort_tmp.device = L.res.device = L.sdefer.device = L.frs.device = L.slist.device = device_;
+            L.sort_tmp.device = L.res.device = L.frs.device = L.slist.device = device_;
     ReflLevel& L1 = refl_[1];
     const bool frames = P.has_reflection;
     if (frames) {

@@ -60,8 +60,6 @@ struct Knobs {
                               // exact mode) take the general kernel, not the plain one (5.8)
     bool fused_ssaa = true;   // RT_FUSED_SSAA=0: band launches downscale in a separate pass (7)
     bool refl_engine = true;  // RT_REFL_ENGINE=0: the one-lane-per-pixel recursive kernel (9)
-    bool refl_sort = true;    // RT_REFL_SORT=0: reflection frames in spawn order, not Morton order
-    bool refl_fuse = true;    // RT_REFL_FUSE=0: the engine's separate list / spawn passes
     int refl_chunk_log2 = 27; // RT_REFL_CHUNK_LOG2 (10..27): sample slots per engine chunk
     bool debug_waves = false; // RT_DEBUG_WAVES: per-wave records of diagnostic builds (rt_debug_read)
     bool exact = false;       // RT_EXACT=1 / rt_set_exact: wbvh and seg off
@@ -82,14 +80,6 @@ struct Knobs {
                               // frame, 1,195 without); 0: refl_trace_kernel with its deferral (RT_REFL_DEFER)
     bool refl_sample_major = true;  // RT_REFL_SAMPLE_MAJOR=0: the engine's slots frame-major (a frame's samples
                               // side by side) instead of sample-major (kernels.hip slot_of)
-    bool refl_feed_frame_order = false; // RT_REFL_FEED_FRAME_ORDER=1: the feed hands out a frame's samples together
-                              // over the sample-major slots (C5 977 vs 965 ms per frame: not faster)
-    bool refl_dir_sort = false;  // RT_REFL_DIR_SORT=1: the feed takes its slots grouped by direction bin
-                              // (kernels.hip refl_dir_keys_kernel, ReflArgs::perm)
-    bool refl_feed_xcd = true;  // RT_REFL_FEED_XCD=0: one ticket over all the feed's slots instead of eighths, a wave
-                              // starting on its XCD's (kernels.hip ReflFeed::fetch, ReflArgs::feed_parts)
-    bool refl_defer_sort = false;  // RT_REFL_DEFER_SORT=1: the long kernel takes the deferred queries in their
-                              // frames' order (refl_defer_keys_kernel; measured slower)
     bool refl_shadow_sort = true;  // RT_REFL_SHADOW_SORT=0: the engine's shadow pass takes its list in the order
                               // pass1 appended it, not sorted by hit point (kernels.hip refl_shadow_keys_kernel)
     bool refl_sorted_frames = true;  // RT_REFL_SORTED_FRAMES=0: the engine reads frames through the sort order
@@ -98,9 +88,6 @@ struct Knobs {
                               // case (b), wbvh.hpp risk_cap_skip)
     bool ocone = true;        // RT_OCONE=0: no origin cones (reflection queries always run case (b), ocone.hpp)
     int ocone_dim = 128;      // RT_OCONE_DIM=n: the origin-cone grid's cells along the scene's longest axis
-    int refl_shadow_feed = 0; // RT_REFL_SHADOW_FEED=k: the engine's shadow pass by refl_shadow_feed_kernel (lane
-                              // refill at k waiting lanes; fused engine only; C5 16 / 24 / 32 / 48: 1,154 / 1,118 /
-                              // 1,094 / 1,078 ms per frame, 1,079 without); 0: refl_shadow_kernel per entry
     int inject_fail = 0;      // RT_INJECT_FRAME_FAIL=k (tests): the k-th ray_trace fails after its image start
     bool async_accel = true;  // RT_ASYNC_ACCEL=0: the leaf cones / slabs and the wide BVH are built
                               // before the first frame instead of beside it
@@ -368,7 +355,7 @@ private:
 
     // reflection engine buffers, per level (frames, results, chunk samples / hits, child counter)
     struct ReflLevel {
-        DevBuf fr, ret, sm, hit, cnt, list, sort, sort_tmp, res, sdefer, frs, slist;
+        DevBuf fr, ret, sm, hit, cnt, list, sort, sort_tmp, res, frs, slist;
     };
     static constexpr int REFL_LEVELS = 18;   // max_recursion_depth <= 15: frames at levels 1..16, +1 child slot
     ReflLevel refl_[REFL_LEVELS];

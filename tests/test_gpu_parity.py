@@ -378,11 +378,11 @@ def test_reflection_engine_matches_oracle_c5_small(make_renderer):
     sc, st = scenes.sphere1m_refl(width=64, height=36, samples=4)
     st = st.copy(max_recursion_depth=3)
     o = Oracle(sc, st).render_rows()
-    # (engine, fused passes, chunk log2): the default engine, its separate list / spawn passes,
-    # many small chunks per level (depth-first over chunks), and the recursive kernel
-    for engine, fuse, clog in (("1", "1", "24"), ("1", "0", "24"), ("1", "1", "10"), ("0", "1", "24")):
-        R = make_renderer(RT_REFL_ENGINE=engine, RT_REFL_FUSE=fuse, RT_REFL_CHUNK_LOG2=clog)
-        engine = f"engine {engine} fuse {fuse} chunk 2^{clog}"
+    # (engine, chunk log2): the default engine, many small chunks per level (depth-first over
+    # chunks), and the recursive kernel
+    for engine, clog in (("1", "24"), ("1", "10"), ("0", "24")):
+        R = make_renderer(RT_REFL_ENGINE=engine, RT_REFL_CHUNK_LOG2=clog)
+        engine = f"engine {engine} chunk 2^{clog}"
         g = gpu_render(R, sc, st)
         assert np.array_equal(g["hit_id"], o.hit_id), engine
         assert np.array_equal(bits(g["hit_t"]), bits(o.hit_t)), engine
