@@ -49,6 +49,7 @@ __device__ __forceinline__ void w_step_hook(uint32_t cur, int leaf)
 #include "kparams.hpp"
 #include "rt_math.hpp"
 #include "wbvh.hpp"
+#include "launch.hpp"
 
 namespace rt {
 
@@ -951,6 +952,59 @@ __device__ __noinline__ WDeep wide_closest_deep(const WNode* wnodes, const GTri*
     return r;
 }
 
+// the wide query's margin m for a ray from o (wbvh.hpp wbvh_closest)
+__device__ __forceinline__ float wide_margin(const KParams& P, v3 o)
+{
+    const float om = fmaxf(fabsf(o.x), fmaxf(fabsf(o.y), fabsf(o.z)));
+    return 0x1p-16f * (om + P.scene_scale);
+}
+
+// wbvh_closest on the lane's LDS stack (Stk over lv), and again through wide_closest_deep when that
+// overflows.  count: the query kind's first word for count_wave_steps (RT_COUNT builds; < 0: the query
+// is not counted)
+template <class Stk, int G>
+__device__ __forceinline__ int wide_run(const KParams& P, v3 o, v3 d, uint2* lv, WHit& w, float hi, bool ties, float QS,
+                                        const uint64_t* rk, int rsel, float rsub, uint32_t max_steps, bool nob, int count)
+{
+    const float m = wide_margin(P, o);
+    Stk stk{lv};
+#if RT_COUNT
+    uint32_t work[4] = {0, 0, 0, 0};
+    uint32_t* wk = count >= 0 ? work : nullptr;
+#else
+    uint32_t* wk = nullptr;
+#endif
+    int st = wbvh_closest<Stk, G>(P.wnodes, P.wtris, o, d, m, stk, w, wk, hi, ties, QS, rk, rsel, rsub, max_steps,
+                                  (WNoFeed*)nullptr, nob);
+#if RT_COUNT
+    if (wk) {
+        count_wave_steps(P, count, wk[3]);
+        if (P.counters) {
+            atomicAdd(&P.counters[10], (unsigned long long)wk[0]);
+            atomicAdd(&P.counters[11], (unsigned long long)wk[1]);
+            for (int c = 0; c < 5; c++)
+                if ((wk[2] >> c) & 1u)
+                    atomicAdd(&P.counters[16 + c], 1ull);   // uncertified, by reason (wbvh_closest)
+        }
+    }
+#endif
+    if (st == W_DEEP) {
+        const WDeep r = wide_closest_deep(P.wnodes, P.wtris, o, d, m, hi, ties, QS, rk, rsel, rsub);
+        st = r.st;
+        w = r.w;
+    }
+    return st;
+}
+
+// The certificate of the wide query's hit w: the octree leaf holding the triangle passes the reference's
+// k-DOP test at t* (bvh.h:79-105).  M: one 16-B load names the slot, the certificate's leaf, the index
+// and the material.
+__device__ __forceinline__ bool wide_certified(const KParams& P, const WHit& w, v3 o, v3 d, uint4& M)
+{
+    M = ldg(P.wmeta + w.k);
+    return kdop_certifies(load_gnode(P.nodes + M.y), o, d, w.t);
+}
+
 // BVH::intersect through the wide BVH and its certificate (wbvh.hpp).
 // Returns true with (h, r) = the reference's record and boolean when the query is
 // certified; false when it must be traced through the octree.
@@ -961,38 +1015,17 @@ __device__ __forceinline__ bool wide_closest(const KParams& P, v3 o, v3 d, THit&
                                              Rec* rec = nullptr, uint32_t max_steps = 0, bool* longq = nullptr)
 {
     using Stk = WStackLdsN<G == 1 ? CAP : W_STACK>;   // (a lane group's ring: W_STACK entries)
-    const float om = fmaxf(fabsf(o.x), fmaxf(fabsf(o.y), fabsf(o.z)));
-    Stk stk{lv};
     WHit w;
     // a ray from the camera position reads the frame's camera risk keys
     const uint64_t* rk = P.wrisk && o.x == P.cam_pos[0] && o.y == P.cam_pos[1] && o.z == P.cam_pos[2] ? P.wrisk : nullptr;
     // the camera's risk cap: a ray into the silhouette's interior meets no at-risk triangle in case (b)
     const bool nob = rk && P.risk_cap && risk_cap_skip(P.risk_cap[0], P.cap_dir[0], d, W_QS_CLOSEST);
-#if RT_COUNT
-    uint32_t wk[4] = {0, 0, 0, 0};
-    int st = wbvh_closest<Stk, G>(P.wnodes, P.wtris, o, d, 0x1p-16f * (om + P.scene_scale), stk, w, wk, INFINITY, true,
-                          W_QS_CLOSEST, rk, 0, 0.0f, 0u, (WNoFeed*)nullptr, nob);
-    count_wave_steps(P, 22, wk[3]);
-    if (P.counters) {
-        atomicAdd(&P.counters[10], (unsigned long long)wk[0]);
-        atomicAdd(&P.counters[11], (unsigned long long)wk[1]);
-        for (int c = 0; c < 5; c++)
-            if ((wk[2] >> c) & 1u)
-                atomicAdd(&P.counters[16 + c], 1ull);   // uncertified, by reason (wbvh_closest)
-    }
-#else
-    int st = wbvh_closest<Stk, G>(P.wnodes, P.wtris, o, d, 0x1p-16f * (om + P.scene_scale), stk, w, nullptr, INFINITY,
-                          true, W_QS_CLOSEST, rk, 0, 0.0f, max_steps, (WNoFeed*)nullptr, nob);
-#endif
-    if (st == W_LONG) {
+    // (RT_COUNT builds pass no step limit, deliberately: they defer no query and count each to its end)
+    const int st = wide_run<Stk, G>(P, o, d, lv, w, INFINITY, true, W_QS_CLOSEST, rk, 0, 0.0f, RT_COUNT ? 0u : max_steps,
+                                    nob, 22);
+    if (max_steps && st == W_LONG) {   // (only a query with a step limit comes back long)
         *longq = true;
         return false;
-    }
-    if (st == W_DEEP) {
-        const WDeep r = wide_closest_deep(P.wnodes, P.wtris, o, d, 0x1p-16f * (om + P.scene_scale), INFINITY, true,
-                                          W_QS_CLOSEST, rk, 0, 0.0f);
-        st = r.st;
-        w = r.w;
     }
     if (st == W_MISS) {
         h.t = -1.0f;
@@ -1006,20 +1039,16 @@ __device__ __forceinline__ bool wide_closest(const KParams& P, v3 o, v3 d, THit&
     if (st == W_HIT && P.counters)
         atomicAdd(&P.counters[14], 1ull);   // the certificate's k-DOP test
 #endif
-    if (st == W_HIT) {
-        // one 16-B load names the slot, the certificate's leaf, the index and the material
-        const uint4 M = ldg(P.wmeta + w.k);
-        const GNode leaf = load_gnode(P.nodes + M.y);
-        if (kdop_certifies(leaf, o, d, w.t)) {
-            h.t = w.t;
-            h.u = w.u;
-            h.v = w.v;
-            h.k = (int32_t)M.x;
-            r = true;
-            if (rec)
-                *rec = rec_of(P, load_gtri(P.wtris + w.k), (int)M.z, (int)M.w, h);
-            return true;
-        }
+    uint4 M;
+    if (st == W_HIT && wide_certified(P, w, o, d, M)) {
+        h.t = w.t;
+        h.u = w.u;
+        h.v = w.v;
+        h.k = (int32_t)M.x;
+        r = true;
+        if (rec)
+            *rec = rec_of(P, load_gtri(P.wtris + w.k), (int)M.z, (int)M.w, h);
+        return true;
     }
 #if RT_COUNT
     if (P.counters) {
@@ -1043,8 +1072,6 @@ __device__ __forceinline__ bool wide_shadow(const KParams& P, v3 o, v3 d, float 
                                             bool light)
 {
     using Stk = WStackLdsN<G == 1 ? CAP : W_STACK>;
-    const float om = fmaxf(fabsf(o.x), fmaxf(fabsf(o.y), fabsf(o.z)));
-    Stk stk{lv};
     WHit w;
     const uint64_t* rk = light ? P.wrisk : nullptr;
     const float rsub = light ? wrisk_sub(W_QS_SHADOW, hi, P.risk_nu) : 0.0f;
@@ -1052,28 +1079,7 @@ __device__ __forceinline__ bool wide_shadow(const KParams& P, v3 o, v3 d, float 
     // the origin face away from it; ocone.hpp, built for W_QS_CLOSEST >= W_QS_SHADOW, so for a superset)
     static_assert(W_QS_SHADOW <= W_QS_CLOSEST, "the origin cones hold the at-risk triangles for the larger split");
     const bool nob = ocone_skip(P.ocone, o, d, W_QS_SHADOW) || (light && P.risk_cap && risk_cap_skip(P.risk_cap[1], P.cap_dir[1], d, W_QS_SHADOW));
-#if RT_COUNT
-    uint32_t wk[4] = {0, 0, 0, 0};
-    int st = wbvh_closest<Stk, G>(P.wnodes, P.wtris, o, d, 0x1p-16f * (om + P.scene_scale), stk, w, wk, hi, false,
-                          W_QS_SHADOW, rk, 1, rsub, 0u, (WNoFeed*)nullptr, nob);
-    count_wave_steps(P, 25, wk[3]);
-    if (P.counters) {
-        atomicAdd(&P.counters[10], (unsigned long long)wk[0]);
-        atomicAdd(&P.counters[11], (unsigned long long)wk[1]);
-        for (int c = 0; c < 5; c++)
-            if ((wk[2] >> c) & 1u)
-                atomicAdd(&P.counters[16 + c], 1ull);   // uncertified, by reason (wbvh_closest)
-    }
-#else
-    int st = wbvh_closest<Stk, G>(P.wnodes, P.wtris, o, d, 0x1p-16f * (om + P.scene_scale), stk, w, nullptr, hi, false,
-                          W_QS_SHADOW, rk, 1, rsub, 0u, (WNoFeed*)nullptr, nob);
-#endif
-    if (st == W_DEEP) {
-        const WDeep r = wide_closest_deep(P.wnodes, P.wtris, o, d, 0x1p-16f * (om + P.scene_scale), hi, false, W_QS_SHADOW,
-                                          rk, 1, rsub);
-        st = r.st;
-        w = r.w;
-    }
+    const int st = wide_run<Stk, G>(P, o, d, lv, w, hi, false, W_QS_SHADOW, rk, 1, rsub, 0u, nob, 25);
     if (st == W_MISS) {
         *sh = false;
         return true;
@@ -1082,7 +1088,8 @@ __device__ __forceinline__ bool wide_shadow(const KParams& P, v3 o, v3 d, float 
     if (st == W_HIT && P.counters)
         atomicAdd(&P.counters[14], 1ull);
 #endif
-    if (st == W_HIT && kdop_certifies(load_gnode(P.nodes + ldg(P.wmeta + w.k).y), o, d, w.t)) {
+    uint4 M;
+    if (st == W_HIT && wide_certified(P, w, o, d, M)) {
         v3 q = o + d * w.t;
         *sh = length2(p - q) < length2(p - lp);
         return true;
@@ -1147,12 +1154,20 @@ __device__ __noinline__ OctQ octree_query_call(const KParams& P, v3 o, v3 d, flo
     return octree_query_inl(P, o, d, lo, hi, seg, lv);
 }
 
-// The launch's KParams where the kernel received it (the plain kernel takes KParams as its first
-// argument, at offset 0 of the kernel-argument segment): passing the kernel's by-value copy to a
-// call would copy all of it into scratch first.
+// The launch's KParams where the kernel received it (every kernel that reads it this way takes KParams
+// as its first argument, at offset 0 of the kernel-argument segment, and leaves that argument unused):
+// passing the kernel's by-value copy to a call made every lane copy all of it into scratch first (r05:
+// C5's shadow pass wrote ~90 GB per launch).
 __device__ __forceinline__ const KParams& kernel_params()
 {
     return *reinterpret_cast<const KParams*>((const void*)__builtin_amdgcn_kernarg_segment_ptr());
+}
+
+// the lane's entries of the launch's dynamic LDS (lds_bytes): entry i at [i * BLOCK]
+__device__ __forceinline__ uint2* lane_stack()
+{
+    extern __shared__ uint2 lds_levels[];
+    return lds_levels + threadIdx.x;
 }
 
 template <bool CALL>
@@ -1818,35 +1833,6 @@ __device__ __forceinline__ void tile_stats_flush(const KParams& P, int lane)
     if (m) atomicMax(P.tile_stats + 1, (unsigned long long)m);
 }
 
-__device__ __forceinline__ int tile_queue_next_shards(const KParams& P);
-
-// The next tile: first the heavy list (one global ticket per tile), then the sharded queue with the
-// heavy tiles skipped (each tile exactly once; the split tiles of heavy_prep_kernel are
-// trace_split_part's).
-__device__ __forceinline__ int tile_queue_next(const KParams& P)
-{
-    const int lane = threadIdx.x & 63;
-    if (P.heavy_list) {
-        if (!__builtin_amdgcn_readfirstlane(__hip_atomic_load(&g_bq.heavy_done, __ATOMIC_RELAXED,
-                                                             __HIP_MEMORY_SCOPE_WORKGROUP))) {
-            int t = 0;
-            if (lane == 0)
-                t = atomicAdd(P.heavy_ctr + 1, 1);
-            t = __builtin_amdgcn_readfirstlane(t);
-            if (t < min(ldg(P.heavy_ctr), P.tiles_x * P.tiles_y / 16))   // (heavy_prep_kernel counts past its cap)
-                return ldg(P.heavy_list + t);
-            if (lane == 0)
-                __hip_atomic_store(&g_bq.heavy_done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-        for (;;) {
-            const int tile = tile_queue_next_shards(P);
-            if (tile < 0 || !((ldg(P.heavy_bits + (tile >> 5)) >> (tile & 31)) & 1u))
-                return tile;
-        }
-    }
-    return tile_queue_next_shards(P);
-}
-
 __device__ __forceinline__ int tile_queue_next_shards(const KParams& P)
 {
     const int lane = threadIdx.x & 63;
@@ -1902,6 +1888,33 @@ __device__ __forceinline__ int tile_queue_next_shards(const KParams& P)
             __builtin_amdgcn_s_sleep(2);
         }
     }
+}
+
+// The next tile: first the heavy list (one global ticket per tile), then the sharded queue with the
+// heavy tiles skipped (each tile exactly once; the split tiles of heavy_prep_kernel are
+// trace_split_part's).
+__device__ __forceinline__ int tile_queue_next(const KParams& P)
+{
+    const int lane = threadIdx.x & 63;
+    if (P.heavy_list) {
+        if (!__builtin_amdgcn_readfirstlane(__hip_atomic_load(&g_bq.heavy_done, __ATOMIC_RELAXED,
+                                                             __HIP_MEMORY_SCOPE_WORKGROUP))) {
+            int t = 0;
+            if (lane == 0)
+                t = atomicAdd(P.heavy_ctr + 1, 1);
+            t = __builtin_amdgcn_readfirstlane(t);
+            if (t < min(ldg(P.heavy_ctr), P.tiles_x * P.tiles_y / 16))   // (heavy_prep_kernel counts past its cap)
+                return ldg(P.heavy_list + t);
+            if (lane == 0)
+                __hip_atomic_store(&g_bq.heavy_done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        for (;;) {
+            const int tile = tile_queue_next_shards(P);
+            if (tile < 0 || !((ldg(P.heavy_bits + (tile >> 5)) >> (tile & 31)) & 1u))
+                return tile;
+        }
+    }
+    return tile_queue_next_shards(P);
 }
 
 // The wave's instruction-issue priority among the waves of its SIMD: heavy-list tiles carry a level
@@ -2049,8 +2062,7 @@ __global__ __launch_bounds__(BLOCK, OCT ? RT_OCC_OCT : PLAIN ? RT_OCC_PLAIN : RT
     auto kp = __builtin_amdgcn_kernarg_segment_ptr();
     (void)P_arg;
     const KParams& P = *reinterpret_cast<const KParams*>((const void*)kp);
-    extern __shared__ uint2 lds_levels[];
-    uint2* lv = lds_levels + threadIdx.x;
+    uint2* lv = lane_stack();
     int lane = threadIdx.x & 63;
     unsigned nshadow = 0, nrefl = 0;
     tile_queue_init();
@@ -2169,6 +2181,19 @@ __device__ __forceinline__ void wave_count_add(unsigned long long* ctr, unsigned
         atomicAdd(ctr, (unsigned long long)v);
 }
 
+// Append to a list from (possibly divergent) lanes: the lanes where lead holds take consecutive indices
+// from *counter with one atomic per wave; returns the lane's index (every active lane calls it)
+__device__ __forceinline__ uint32_t wave_append(unsigned int* counter, bool lead = true)
+{
+    const uint64_t m = __ballot(lead);
+    const int leader = __ffsll((unsigned long long)m) - 1;
+    uint32_t base = 0;
+    if ((int)(threadIdx.x & 63) == leader)
+        base = atomicAdd(counter, (unsigned)__popcll(m));
+    base = __shfl(base, leader);
+    return base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
 // compute_reflection prologue (renderer.cpp:285-296) for the hit record h
 __device__ __forceinline__ float frame_roughness(const KParams& P, const Rec& h, const float* m)
 {
@@ -2204,12 +2229,9 @@ __device__ __forceinline__ void make_frame(const KParams& P, FrameRec& F, v3 ip,
 // reflective hit becomes a level-1 frame, any other pixel is finished here.
 __global__ __launch_bounds__(BLOCK, RT_OCC) void refl_level0_kernel(KParams P_arg, FrameRec* fr1, unsigned int* nfr1)
 {
-    // the parameters where the kernel received them (not a copy: passing the by-value argument to a
-    // call made every lane copy it to scratch, r05: C5's shadow pass wrote ~90 GB per launch)
     const KParams& P = kernel_params();
     (void)P_arg;
-    extern __shared__ uint2 lds_levels[];
-    uint2* lv = lds_levels + threadIdx.x;
+    uint2* lv = lane_stack();
     int lane = threadIdx.x & 63;
     const int ntiles = P.tiles_x * P.tiles_y;
     v3 cam = mk(P.cam_pos[0], P.cam_pos[1], P.cam_pos[2]);
@@ -2394,18 +2416,54 @@ __device__ __forceinline__ void refl_no_ray(const ReflArgs& A, int slot, v3 dir)
 #define RT_OCC_REFL 4   // waves per SIMD of the reflection trace / shadow / pass1 kernels (r04, the sound query:
                         // C5 689 vs 656 Mrays/s at 5 (31 spills), 691 at 3; r03: 4 -> 5 about -0.6%)
 #endif
-template <int G = 1>
+// One reflection sample's closest hit into A.hit[slot]; a query past max_steps (> 0) goes to the
+// deferred list instead.
+// In line, with the octree fallback behind the out-of-line octree_query_call (results by value): a
+// ray record or hit record whose address reached a call lived in scratch for every sample (r05).
+// G > 1 (refl_trace_long_kernel): the G lanes of a group hold the same slot and run the query
+// together; the group's first lane writes the result.
+template <int G>
 __device__ __forceinline__ void refl_trace_one(const KParams& P, const ReflArgs& A, int slot, v3 dir, uint2* lv,
-                                               uint32_t max_steps);
+                                               uint32_t max_steps)
+{
+    const FrameRec& F = refl_frame(A, slot_pos(A, slot));
+    const v3 ro = ld3(F.ro);
+    THit h;
+    bool r;
+    bool longq = false;
+    if (P.wnodes && P.nnodes > 0 && !ray_is_nan(ro, dir) && wide_closest<G>(P, ro, dir, h, r, lv, nullptr, max_steps, &longq))
+        ;   // certified by the wide BVH (DESIGN.md 5.6)
+    else if (longq) {
+        // the groups deferring now (their first lanes): one atomic per wave
+        const bool lead = G == 1 || (threadIdx.x & (G - 1)) == 0;
+        const uint32_t k = wave_append(A.defer_count, lead);
+        if (lead)
+            A.defer[k] = slot;
+        return;
+    } else {
+        const bool seg = P.seg_scale > 0.0f && P.seg_oct;
+        // (seg: nothing behind the origin can be hit, t >= 0)
+        const float lo = seg ? -seg_margin(P, make_ray(P, ro, dir)) : 0.0f;
+        const OctQ q = octree_query<true>(P, ro, dir, lo, INFINITY, seg, lv);
+        h = q.h;
+        r = q.r;
+    }
+    RawHit H;
+    H.t = h.t;
+    H.u = h.u;
+    H.v = h.v;
+    H.k = h.k;
+    st3(H.d, dir);
+    H.r = (r ? 1 : 0) | 2;
+    if (G == 1 || (threadIdx.x & (G - 1)) == 0)
+        A.hit[slot] = H;
+}
 
 __global__ __launch_bounds__(BLOCK, RT_OCC_REFL) void refl_trace_kernel(KParams P_arg, ReflArgs A)
 {
-    // the parameters where the kernel received them (not a copy: passing the by-value argument to a
-    // call made every lane copy it to scratch, r05: C5's shadow pass wrote ~90 GB per launch)
     const KParams& P = kernel_params();
     (void)P_arg;
-    extern __shared__ uint2 lds_levels[];
-    uint2* lv = lds_levels + threadIdx.x;
+    uint2* lv = lane_stack();
     constexpr int G = RT_REFL_G;   // lanes per sample (the launch has G threads per slot)
     const bool lead = G == 1 || (threadIdx.x & (G - 1)) == 0;
     int slot = (int)((blockIdx.x * BLOCK + threadIdx.x) / G);
@@ -2457,16 +2515,7 @@ struct ReflFeed {
     int nslot;
 
     // defer the lanes' slots (divergent lanes: one atomic per wave)
-    __device__ __forceinline__ void defer() const
-    {
-        const uint64_t mk = __ballot(1);
-        const int leader = __ffsll((unsigned long long)mk) - 1;
-        uint32_t base = 0;
-        if ((int)(threadIdx.x & 63) == leader)
-            base = atomicAdd(A->defer_count, (unsigned)__popcll(mk));
-        base = __shfl(base, leader);
-        A->defer[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk, 0u))] = slot;
-    }
+    __device__ __forceinline__ void defer() const { A->defer[wave_append(A->defer_count)] = slot; }
 
     __device__ __forceinline__ void finish(int st, WHit& w, v3 o, v3 d)
     {
@@ -2477,17 +2526,13 @@ struct ReflFeed {
         H.u = 1.0f;
         H.v = 0.0f;
         bool r = false, ok = st == W_MISS;
-        if (st == W_HIT) {
-            // the certificate (wide_closest): the octree leaf holding the triangle passes the reference's
-            // k-DOP test at t* (bvh.h:79-105)
-            const uint4 M = ldg(P->wmeta + w.k);
-            if (kdop_certifies(load_gnode(P->nodes + M.y), o, d, w.t)) {
-                H.t = w.t;
-                H.u = w.u;
-                H.v = w.v;
-                H.k = (int32_t)M.x;
-                r = ok = true;
-            }
+        uint4 M;
+        if (st == W_HIT && wide_certified(*P, w, o, d, M)) {
+            H.t = w.t;
+            H.u = w.u;
+            H.v = w.v;
+            H.k = (int32_t)M.x;
+            r = ok = true;
         }
         if (!ok) {
             defer();
@@ -2551,8 +2596,7 @@ struct ReflFeed {
             defer();
             return false;
         }
-        const float om = fmaxf(fabsf(o.x), fmaxf(fabsf(o.y), fabsf(o.z)));
-        m = 0x1p-16f * (om + P->scene_scale);
+        m = wide_margin(*P, o);
         nob = ocone_skip(P->ocone, o, d, W_QS_CLOSEST);
         busy = true;
         return true;
@@ -2563,8 +2607,7 @@ __global__ __launch_bounds__(BLOCK, RT_OCC_FEED) void refl_trace_feed_kernel(KPa
 {
     const KParams& P = kernel_params();
     (void)P_arg;
-    extern __shared__ uint2 lds_levels[];
-    uint2* lv = lds_levels + threadIdx.x;
+    uint2* lv = lane_stack();
     ReflFeed feed;
     feed.threshold = A.feed;
     feed.P = &P;
@@ -2602,12 +2645,9 @@ __global__ __launch_bounds__(BLOCK, RT_OCC_REFL) void refl_trace_long_kernel(KPa
 {
     constexpr int G = RT_REFL_LONG_G;
     static_assert(G == 1 || G == 2 || G == 4 || G == 8, "lane groups of 1, 2, 4 or 8");
-    // the parameters where the kernel received them (not a copy: passing the by-value argument to a
-    // call made every lane copy it to scratch, r05: C5's shadow pass wrote ~90 GB per launch)
     const KParams& P = kernel_params();
     (void)P_arg;
-    extern __shared__ uint2 lds_levels[];
-    uint2* lv = lds_levels + threadIdx.x;
+    uint2* lv = lane_stack();
     const int n = (int)ldg(A.defer_count);
     // a wave takes the next 64 / G queries from a ticket (defer_count[1], zeroed with the count) when it
     // is done with its last ones: the waves' batches differ in length, a fixed grid stride left the
@@ -2631,71 +2671,12 @@ __global__ __launch_bounds__(BLOCK, RT_OCC_REFL) void refl_trace_long_kernel(KPa
     }
 }
 
-// One reflection sample's closest hit into A.hit[slot]; a query past max_steps (> 0) goes to the
-// deferred list instead.
-// In line, with the octree fallback behind the out-of-line octree_query_call (results by value): a
-// ray record or hit record whose address reached a call lived in scratch for every sample (r05).
-// G > 1 (refl_trace_long_kernel): the G lanes of a group hold the same slot and run the query
-// together; the group's first lane writes the result.
-template <int G>
-__device__ __forceinline__ void refl_trace_one(const KParams& P, const ReflArgs& A, int slot, v3 dir, uint2* lv,
-                                               uint32_t max_steps)
-{
-    const FrameRec& F = refl_frame(A, slot_pos(A, slot));
-    const v3 ro = ld3(F.ro);
-    THit h;
-    bool r;
-    bool longq = false;
-    if (P.wnodes && P.nnodes > 0 && !ray_is_nan(ro, dir) && wide_closest<G>(P, ro, dir, h, r, lv, nullptr, max_steps, &longq))
-        ;   // certified by the wide BVH (DESIGN.md 5.6)
-    else if (longq) {
-        // the groups deferring now (their first lanes): one atomic per wave
-        const bool lead = G == 1 || (threadIdx.x & (G - 1)) == 0;
-        const uint64_t m = __ballot(lead);
-        const int leader = __ffsll((unsigned long long)m) - 1;
-        uint32_t base = 0;
-        if ((int)(threadIdx.x & 63) == leader)
-            base = atomicAdd(A.defer_count, (unsigned)__popcll(m));
-        base = __shfl(base, leader);
-        if (lead)
-            A.defer[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = slot;
-        return;
-    } else {
-        const bool seg = P.seg_scale > 0.0f && P.seg_oct;
-        // (seg: nothing behind the origin can be hit, t >= 0)
-        const float lo = seg ? -seg_margin(P, make_ray(P, ro, dir)) : 0.0f;
-        const OctQ q = octree_query<true>(P, ro, dir, lo, INFINITY, seg, lv);
-        h = q.h;
-        r = q.r;
-    }
-    RawHit H;
-    H.t = h.t;
-    H.u = h.u;
-    H.v = h.v;
-    H.k = h.k;
-    st3(H.d, dir);
-    H.r = (r ? 1 : 0) | 2;
-    if (G == 1 || (threadIdx.x & (G - 1)) == 0)
-        A.hit[slot] = H;
-}
-
 // append slot to the shadow list from (possibly divergent) lanes: one atomic per wave
-__device__ __forceinline__ void list_append(const ReflArgs& A, int slot)
-{
-    const uint64_t m = __ballot(1);   // the lanes appending now
-    const int leader = __ffsll((unsigned long long)m) - 1;
-    uint32_t base = 0;
-    if ((int)(threadIdx.x & 63) == leader)
-        base = atomicAdd(A.list_count, (unsigned)__popcll(m));
-    base = __shfl(base, leader);
-    A.list[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = slot;
-}
+__device__ __forceinline__ void list_append(const ReflArgs& A, int slot) { A.list[wave_append(A.list_count)] = slot; }
 
 // pass1: per frame, the samples' trace_ray up to the shadow query, in sample order
 __global__ __launch_bounds__(BLOCK, RT_OCC_REFL) void refl_pass1_kernel(KParams P_arg, ReflArgs A)
 {
-    // the parameters where the kernel received them (not a copy: passing the by-value argument to a
-    // call made every lane copy it to scratch, r05: C5's shadow pass wrote ~90 GB per launch)
     const KParams& P = kernel_params();
     (void)P_arg;
     int p = A.c0 + blockIdx.x * BLOCK + threadIdx.x;
@@ -2743,7 +2724,22 @@ __global__ __launch_bounds__(BLOCK, RT_OCC_REFL) void refl_pass1_kernel(KParams 
     wave_count_add(&P.counters[0], nshadow);
 }
 
-__device__ __forceinline__ int spawn_sample(const KParams& P, const ReflArgs& A, int slot, SampleRec& S, bool sh);
+// a shaded sample with a reflective material becomes a frame of the next level (its
+// compute_reflection call); the frame's index goes into S.child
+__device__ __forceinline__ int spawn_sample(const KParams& P, const ReflArgs& A, int slot, SampleRec& S, bool sh)
+{
+    const float* m = mat_of(P, S.mat);
+    if (!(m[12] > 0.0f))
+        return -1;
+    const int i = slot_sample(A, slot);
+    const FrameRec& F = refl_frame(A, slot_pos(A, slot));
+    unsigned idx = atomicAdd(A.child_count, 1u);
+    c3 dfc = shade_shadow_emit(P, ldc(S.fc), m, sh);
+    make_frame(P, A.child_fr[idx], ld3(S.ip), ld3(S.nrm), ld3(A.hit[slot].d), dfc, S.crough, S.mat,
+               child_key(F.key, (uint32_t)i), -1);
+    S.child = (int)idx;
+    return (int)idx;
+}
 
 // a sample's shadow decided: its record, the child frame it spawns and the colour it returns
 __device__ __forceinline__ void refl_shadow_done(const KParams& P, const ReflArgs& A, int slot, bool sh)
@@ -2766,12 +2762,9 @@ __device__ __forceinline__ void refl_shadow_done(const KParams& P, const ReflArg
 #endif
 __global__ __launch_bounds__(BLOCK, RT_OCC_REFL) void refl_shadow_kernel(KParams P_arg, ReflArgs A)
 {
-    // the parameters where the kernel received them (not a copy: passing the by-value argument to a
-    // call made every lane copy it to scratch, r05: C5's shadow pass wrote ~90 GB per launch)
     const KParams& P = kernel_params();
     (void)P_arg;
-    extern __shared__ uint2 lds_levels[];
-    uint2* lv = lds_levels + threadIdx.x;
+    uint2* lv = lane_stack();
     unsigned t = blockIdx.x * BLOCK + threadIdx.x;
     if (t >= *A.list_count)
         return;
@@ -2783,28 +2776,9 @@ __global__ __launch_bounds__(BLOCK, RT_OCC_REFL) void refl_shadow_kernel(KParams
     refl_shadow_done(P, A, A.list[t], sh);
 }
 
-// a shaded sample with a reflective material becomes a frame of the next level (its
-// compute_reflection call); the frame's index goes into S.child
-__device__ __forceinline__ int spawn_sample(const KParams& P, const ReflArgs& A, int slot, SampleRec& S, bool sh)
-{
-    const float* m = mat_of(P, S.mat);
-    if (!(m[12] > 0.0f))
-        return -1;
-    const int i = slot_sample(A, slot);
-    const FrameRec& F = refl_frame(A, slot_pos(A, slot));
-    unsigned idx = atomicAdd(A.child_count, 1u);
-    c3 dfc = shade_shadow_emit(P, ldc(S.fc), m, sh);
-    make_frame(P, A.child_fr[idx], ld3(S.ip), ld3(S.nrm), ld3(A.hit[slot].d), dfc, S.crough, S.mat,
-               child_key(F.key, (uint32_t)i), -1);
-    S.child = (int)idx;
-    return (int)idx;
-}
-
 // resolve: compute_reflection's sum in sample order, then the frame's hit colour
 __global__ __launch_bounds__(BLOCK) void refl_resolve_kernel(KParams P_arg, ReflArgs A)
 {
-    // the parameters where the kernel received them (not a copy: passing the by-value argument to a
-    // call made every lane copy it to scratch, r05: C5's shadow pass wrote ~90 GB per launch)
     const KParams& P = kernel_params();
     (void)P_arg;
     int p = A.c0 + blockIdx.x * BLOCK + threadIdx.x;
@@ -3114,12 +3088,9 @@ __global__ __launch_bounds__(BLOCK) void raster_fill_big_kernel(KParams P, Raste
 __global__ __launch_bounds__(BLOCK, RT_OCC) void raster_shade_kernel(KParams P_arg, RasterArgs A,
                                                                      FrameRec* fr1, unsigned int* nfr1)
 {
-    // the parameters where the kernel received them (not a copy: passing the by-value argument to a
-    // call made every lane copy it to scratch, r05: C5's shadow pass wrote ~90 GB per launch)
     const KParams& P = kernel_params();
     (void)P_arg;
-    extern __shared__ uint2 lds_levels[];
-    uint2* lv = lds_levels + threadIdx.x;
+    uint2* lv = lane_stack();
     int lane = threadIdx.x & 63;
     const int ntiles = P.tiles_x * P.tiles_y;
     v3 cam = mk(P.cam_pos[0], P.cam_pos[1], P.cam_pos[2]);
@@ -3451,12 +3422,9 @@ __global__ __launch_bounds__(BLOCK) void trace_rays_kernel(KParams P_arg, const 
                                                            float* __restrict__ out_u, float* __restrict__ out_v,
                                                            uint8_t* __restrict__ out_ret)
 {
-    // the parameters where the kernel received them (not a copy: passing the by-value argument to a
-    // call made every lane copy it to scratch, r05: C5's shadow pass wrote ~90 GB per launch)
     const KParams& P = kernel_params();
     (void)P_arg;
-    extern __shared__ uint2 lds_levels[];
-    uint2* lv = lds_levels + threadIdx.x;
+    uint2* lv = lane_stack();
     int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n)
         return;
@@ -3505,12 +3473,9 @@ __global__ __launch_bounds__(BLOCK, RT_OCC_PLAIN) void wide_query_kernel(KParams
                                                            float* __restrict__ out_t, float* __restrict__ out_u,
                                                            float* __restrict__ out_v, uint8_t* __restrict__ out_sh)
 {
-    // the parameters where the kernel received them (not a copy: passing the by-value argument to a
-    // call made every lane copy it to scratch, r05: C5's shadow pass wrote ~90 GB per launch)
     const KParams& P = kernel_params();
     (void)P_arg;
-    extern __shared__ uint2 lds_levels[];
-    uint2* lv = lds_levels + threadIdx.x;
+    uint2* lv = lane_stack();
     // G > 1: the G lanes of a lane group trace ray i together (wbvh_closest<.., G>)
     const int i = (blockIdx.x * BLOCK + threadIdx.x) / G;
     const bool writer = (threadIdx.x & (G - 1)) == 0;
@@ -3558,18 +3523,10 @@ __global__ __launch_bounds__(BLOCK, RT_OCC_PLAIN) void wide_query_kernel(KParams
     w.u = 1.0f;
     w.v = 0.0f;
     if (P.wnodes && P.nnodes > 0 && !ray_is_nan(o, d)) {
-        const float om = fmaxf(fabsf(o.x), fmaxf(fabsf(o.y), fabsf(o.z)));
-        const float m = 0x1p-16f * (om + P.scene_scale);
-        WStackLds stk{lv};
-        st = wbvh_closest<WStackLds, G>(P.wnodes, P.wtris, o, d, m, stk, w, nullptr, INFINITY, true, QS, rk, rsel, rsub);
-        if (st == W_DEEP) {
-            const WDeep r = wide_closest_deep(P.wnodes, P.wtris, o, d, m, INFINITY, true, QS, rk, rsel, rsub);
-            st = r.st;
-            w = r.w;
-        }
+        st = wide_run<WStackLds, G>(P, o, d, lv, w, INFINITY, true, QS, rk, rsel, rsub, 0u, false, -1);
         if (st == W_HIT) {
-            const uint4 M = ldg(P.wmeta + w.k);
-            if (kdop_certifies(load_gnode(P.nodes + M.y), o, d, w.t))
+            uint4 M;
+            if (wide_certified(P, w, o, d, M))
                 id = (int32_t)M.z;
             else
                 st = W_UNCERT;
@@ -3601,12 +3558,9 @@ __global__ __launch_bounds__(BLOCK, RT_OCC) void trace_colors_kernel(KParams P_a
                                                                      uint8_t* __restrict__ out_found,
                                                                      uint8_t* __restrict__ out_shadow)
 {
-    // the parameters where the kernel received them (not a copy: passing the by-value argument to a
-    // call made every lane copy it to scratch, r05: C5's shadow pass wrote ~90 GB per launch)
     const KParams& P = kernel_params();
     (void)P_arg;
-    extern __shared__ uint2 lds_levels[];
-    uint2* lv = lds_levels + threadIdx.x;
+    uint2* lv = lane_stack();
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     unsigned nshadow = 0, nrefl = 0;
     if (i < n) {
@@ -3741,8 +3695,8 @@ size_t lds_bytes(const KParams& P, bool plain_pixel = false)
 
 }  // namespace rt
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_trace_rays(const rt::KParams* P, const float* o, const float* d, int n, int32_t* id,
-                                           float* t, float* u, float* v, uint8_t* ret, hipStream_t stream)
+hipError_t rt_launch_trace_rays(const rt::KParams* P, const float* o, const float* d, int n, int32_t* id, float* t,
+                                float* u, float* v, uint8_t* ret, hipStream_t stream)
 {
     if (n <= 0)
         return hipSuccess;
@@ -3752,12 +3706,9 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_trace_rays
     return hipGetLastError();
 }
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_wide_query(const rt::KParams* P, const float* o,
-                                                                                 const float* d, int n, int kind,
-                                                                                 float* o_out, float* d_out,
-                                                                                 int32_t* status, int32_t* id, float* t,
-                                                                                 float* u, float* v, uint8_t* sh,
-                                                                                 hipStream_t stream)
+hipError_t rt_launch_wide_query(const rt::KParams* P, const float* o, const float* d, int n, int kind, float* o_out,
+                                float* d_out, int32_t* status, int32_t* id, float* t, float* u, float* v, uint8_t* sh,
+                                hipStream_t stream)
 {
     if (n <= 0)
         return hipSuccess;
@@ -3776,11 +3727,8 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_wide_query
     return hipGetLastError();
 }
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_trace_colors(const rt::KParams* P, bool refl,
-                                                                                   const float* o, const float* d,
-                                                                                   int n, float4* rgba, int32_t* src,
-                                                                                   float* t, uint8_t* found,
-                                                                                   uint8_t* shadow, hipStream_t stream)
+hipError_t rt_launch_trace_colors(const rt::KParams* P, bool refl, const float* o, const float* d, int n, float4* rgba,
+                                  int32_t* src, float* t, uint8_t* found, uint8_t* shadow, hipStream_t stream)
 {
     if (n <= 0)
         return hipSuccess;
@@ -3872,14 +3820,18 @@ static int plain_blocks(const rt::KParams& P)
     return P.max_blocks > 0 ? std::max(1, std::min(blocks, P.max_blocks / 8 * RT_OCC_PLAIN)) : blocks;
 }
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_heavy_prep(const rt::KParams* P, uint32_t* cost,
-                                                                                 int ntiles, int32_t* list,
-                                                                                 uint32_t* bits, int32_t* ctr,
-                                                                                 int32_t* ctr_next,
-                                                                                 const unsigned long long* stats_prev,
-                                                                                 unsigned long long* stats_next,
-                                                                                 float split, int group,
-                                                                                 hipStream_t stream)
+// the other persistent grids: a block per four tiles, at most enough to fill every CU (surplus blocks
+// would find the queue empty)
+static int persistent_blocks(const rt::KParams& P)
+{
+    const int tiles = P.tiles_x * P.tiles_y;
+    const int blocks = (tiles + rt::WAVES_PER_BLOCK - 1) / rt::WAVES_PER_BLOCK;
+    return blocks > P.max_blocks && P.max_blocks > 0 ? P.max_blocks : blocks;
+}
+
+hipError_t rt_launch_heavy_prep(const rt::KParams* P, uint32_t* cost, int ntiles, int32_t* list, uint32_t* bits,
+                                int32_t* ctr, int32_t* ctr_next, const unsigned long long* stats_prev,
+                                unsigned long long* stats_next, float split, int group, hipStream_t stream)
 {
     if (ntiles <= 0)
         return hipSuccess;
@@ -3890,13 +3842,9 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_heavy_prep
     return hipGetLastError();
 }
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_ray_trace(const rt::KParams* P, hipStream_t stream)
+hipError_t rt_launch_ray_trace(const rt::KParams* P, hipStream_t stream)
 {
-    int tiles = P->tiles_x * P->tiles_y;
-    int blocks = (tiles + rt::WAVES_PER_BLOCK - 1) / rt::WAVES_PER_BLOCK;
-    // persistent waves: enough blocks to fill every CU (surplus blocks find the queue empty)
-    if (blocks > P->max_blocks && P->max_blocks > 0)
-        blocks = P->max_blocks;
+    const int blocks = persistent_blocks(*P);
     if (blocks < 1)
         return hipSuccess;
     const bool plain = !P->has_reflection && P->plain && !P->zbuf && !P->nbuf;
@@ -3926,8 +3874,7 @@ __global__ __launch_bounds__(256) void risk_box_init_kernel(float* B, size_t n)
         B[i] = (i % 6) < 3 ? INFINITY : -INFINITY;
 }
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_risk_box_init(float* B, size_t nentries,
-                                                                                    hipStream_t stream)
+hipError_t rt_launch_risk_box_init(float* B, size_t nentries, hipStream_t stream)
 {
     if (nentries > 0)
         hipLaunchKernelGGL(risk_box_init_kernel, dim3((unsigned)((6 * nentries + 255) / 256)), dim3(256), 0, stream, B,
@@ -3935,10 +3882,10 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_risk_box_i
     return hipGetLastError();
 }
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_wide_risk(
-    const rt::GTri* wtris, const uint4* wmeta, const rt::GNode* onodes, const rt::WNode* wnodes, const uint32_t* tri_leaf,
-    const uint32_t* parent, uint32_t* K, float* B, unsigned long long* risk, int n, int nnodes, const rt::WRiskArgs* A,
-    uint32_t* cap, const float* cap_dir, hipStream_t stream)
+hipError_t rt_launch_wide_risk(const rt::GTri* wtris, const uint4* wmeta, const rt::GNode* onodes,
+                               const rt::WNode* wnodes, const uint32_t* tri_leaf, const uint32_t* parent, uint32_t* K,
+                               float* B, unsigned long long* risk, int n, int nnodes, const rt::WRiskArgs* A,
+                               uint32_t* cap, const float* cap_dir, hipStream_t stream)
 {
     rt::RiskCapDirs cd;
     for (int i = 0; i < 6; i++)
@@ -3953,9 +3900,9 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_wide_risk(
     return hipGetLastError();
 }
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_wide_gather(
-    const rt::GTri* tris, const int32_t* slot, const uint32_t* leaf_of_slot, const int32_t* tri_id,
-    const int32_t* tri_mat, int n, rt::GTri* wtris, uint4* wmeta, hipStream_t stream)
+hipError_t rt_launch_wide_gather(const rt::GTri* tris, const int32_t* slot, const uint32_t* leaf_of_slot,
+                                 const int32_t* tri_id, const int32_t* tri_mat, int n, rt::GTri* wtris, uint4* wmeta,
+                                 hipStream_t stream)
 {
     if (n <= 0)
         return hipSuccess;
@@ -3992,11 +3939,9 @@ __global__ __launch_bounds__(256) void ocone_kernel(const OConeEnt* E, const GTr
 }
 }  // namespace rt
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_ocone(const rt::OConeEnt* E, const rt::GTri* tris,
-                                                                     const uint32_t* todo, int n, const float lo[3],
-                                                                     const int32_t dim[3], double h, double r, double slack,
-                                                                     double QS, double cos_cap, uint2* cells,
-                                                                     size_t ncells, hipStream_t stream)
+hipError_t rt_launch_ocone(const rt::OConeEnt* E, const rt::GTri* tris, const uint32_t* todo, int n, const float lo[3],
+                           const int32_t dim[3], double h, double r, double slack, double QS, double cos_cap,
+                           uint2* cells, size_t ncells, hipStream_t stream)
 {
     if (ncells == 0)
         return hipSuccess;
@@ -4018,8 +3963,7 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_ocone(cons
     return hipGetLastError();
 }
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_downscale(const uint32_t* in, int w, int h_rows, int f, uint32_t* out,
-                                          hipStream_t stream)
+hipError_t rt_launch_downscale(const uint32_t* in, int w, int h_rows, int f, uint32_t* out, hipStream_t stream)
 {
     int dw = w / f, dh = h_rows / f;
     if (dw <= 0 || dh <= 0)
@@ -4030,13 +3974,9 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_downscale(
 }
 
 // ---- reflection engine launchers (renderer.cpp drives the levels) ----
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_refl_level0(const rt::KParams* P, rt::FrameRec* fr1,
-                                                                           unsigned int* nfr1, hipStream_t stream)
+hipError_t rt_launch_refl_level0(const rt::KParams* P, rt::FrameRec* fr1, unsigned int* nfr1, hipStream_t stream)
 {
-    int tiles = P->tiles_x * P->tiles_y;
-    int blocks = (tiles + rt::WAVES_PER_BLOCK - 1) / rt::WAVES_PER_BLOCK;
-    if (blocks > P->max_blocks && P->max_blocks > 0)
-        blocks = P->max_blocks;
+    const int blocks = persistent_blocks(*P);
     if (blocks < 1)
         return hipSuccess;
     size_t lds = rt::lds_bytes(*P);
@@ -4044,9 +3984,7 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_refl_level
     return hipGetLastError();
 }
 
-// stage: 1 gen + trace, 7 the deferred long traces, 2 pass1 (+ shadow list), 3 shadow (+ spawn), 5 resolve
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_refl_stage(int stage, const rt::KParams* P,
-                                                                          const rt::ReflArgs* A, hipStream_t stream)
+hipError_t rt_launch_refl_stage(rt::ReflStage stage, const rt::KParams* P, const rt::ReflArgs* A, hipStream_t stream)
 {
     int nframes = A->c1 - A->c0;
     if (nframes <= 0)
@@ -4055,7 +3993,7 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_refl_stage
     dim3 gs((nslot + rt::BLOCK - 1) / rt::BLOCK), gf((nframes + rt::BLOCK - 1) / rt::BLOCK);
     size_t lds = rt::lds_bytes(*P);
     switch (stage) {
-    case 1:
+    case rt::ReflStage::trace:
         if (A->feed > 0)   // persistent waves (lane refill): the reflection kernels' residency
             hipLaunchKernelGGL(rt::refl_trace_feed_kernel,
                                dim3(std::max(1u, std::min<unsigned>(gs.x, (unsigned)(P->max_blocks / 8 * RT_OCC_FEED)))),
@@ -4064,11 +4002,13 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_refl_stage
         else
             hipLaunchKernelGGL(rt::refl_trace_kernel, dim3(gs.x * RT_REFL_G), dim3(rt::BLOCK), lds, stream, *P, *A);
         break;
-    case 7: hipLaunchKernelGGL(rt::refl_trace_long_kernel, dim3(std::min<unsigned>(gs.x, 2048u)), dim3(rt::BLOCK), lds,
-                               stream, *P, *A); break;
-    case 2: hipLaunchKernelGGL(rt::refl_pass1_kernel, gf, dim3(rt::BLOCK), 0, stream, *P, *A); break;
-    case 3: hipLaunchKernelGGL(rt::refl_shadow_kernel, gs, dim3(rt::BLOCK), lds, stream, *P, *A); break;
-    default: hipLaunchKernelGGL(rt::refl_resolve_kernel, gf, dim3(rt::BLOCK), 0, stream, *P, *A); break;
+    case rt::ReflStage::long_:
+        hipLaunchKernelGGL(rt::refl_trace_long_kernel, dim3(std::min<unsigned>(gs.x, 2048u)), dim3(rt::BLOCK), lds, stream,
+                           *P, *A);
+        break;
+    case rt::ReflStage::pass1: hipLaunchKernelGGL(rt::refl_pass1_kernel, gf, dim3(rt::BLOCK), 0, stream, *P, *A); break;
+    case rt::ReflStage::shadow: hipLaunchKernelGGL(rt::refl_shadow_kernel, gs, dim3(rt::BLOCK), lds, stream, *P, *A); break;
+    case rt::ReflStage::resolve: hipLaunchKernelGGL(rt::refl_resolve_kernel, gf, dim3(rt::BLOCK), 0, stream, *P, *A); break;
     }
     return hipGetLastError();
 }
@@ -4085,17 +4025,16 @@ __global__ __launch_bounds__(256) void refl_sort_frames_kernel(const FrameRec* _
 }
 }  // namespace rt
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_refl_sort_frames(const rt::FrameRec* fr, const int32_t* order,
-                                                                                int n, rt::FrameRec* frs, hipStream_t stream)
+hipError_t rt_launch_refl_sort_frames(const rt::FrameRec* fr, const int32_t* order, int n, rt::FrameRec* frs,
+                                      hipStream_t stream)
 {
     if (n > 0)
         hipLaunchKernelGGL(rt::refl_sort_frames_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, fr, order, n, frs);
     return hipGetLastError();
 }
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_refl_shadow_keys(const rt::KParams* P, const rt::SampleRec* sm,
-                                                                                 const int32_t* list, int n, uint32_t* keys,
-                                                                                 hipStream_t stream)
+hipError_t rt_launch_refl_shadow_keys(const rt::KParams* P, const rt::SampleRec* sm, const int32_t* list, int n,
+                                      uint32_t* keys, hipStream_t stream)
 {
     if (n > 0)
         hipLaunchKernelGGL(rt::refl_shadow_keys_kernel, dim3((n + rt::BLOCK - 1) / rt::BLOCK), dim3(rt::BLOCK), 0, stream, *P,
@@ -4103,9 +4042,8 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_refl_shado
     return hipGetLastError();
 }
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_refl_keys(const rt::KParams* P, const rt::FrameRec* fr,
-                                                                         int n, uint32_t* keys, int32_t* idx,
-                                                                         hipStream_t stream)
+hipError_t rt_launch_refl_keys(const rt::KParams* P, const rt::FrameRec* fr, int n, uint32_t* keys, int32_t* idx,
+                               hipStream_t stream)
 {
     if (n <= 0)
         return hipSuccess;
@@ -4115,42 +4053,32 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_refl_keys(
 }
 
 // ---- raster launchers (renderer.cpp raster path) ----
-// stage: 0 count, 1 write, 2 fill (small pieces), 3 fill (big pieces)
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_raster_stage(int stage, const rt::KParams* P,
-                                                                            const rt::RasterArgs* A, int npieces,
-                                                                            hipStream_t stream)
+hipError_t rt_launch_raster_stage(rt::RasterStage stage, const rt::KParams* P, const rt::RasterArgs* A, int npieces,
+                                  hipStream_t stream)
 {
-    if (stage < 2) {
-        if (A->ntri <= 0)
-            return hipSuccess;
-        dim3 g((unsigned)((A->ntri + rt::BLOCK - 1) / rt::BLOCK));
-        if (stage == 0)
-            hipLaunchKernelGGL(rt::raster_count_kernel, g, dim3(rt::BLOCK), 0, stream, *P, *A);
-        else
-            hipLaunchKernelGGL(rt::raster_write_kernel, g, dim3(rt::BLOCK), 0, stream, *P, *A);
-    } else if (stage == 2) {
-        if (npieces <= 0)
-            return hipSuccess;
+    const bool per_tri = stage == rt::RasterStage::count || stage == rt::RasterStage::write;
+    if ((per_tri ? A->ntri : npieces) <= 0)
+        return hipSuccess;
+    const dim3 g((unsigned)((A->ntri + rt::BLOCK - 1) / rt::BLOCK));
+    switch (stage) {
+    case rt::RasterStage::count: hipLaunchKernelGGL(rt::raster_count_kernel, g, dim3(rt::BLOCK), 0, stream, *P, *A); break;
+    case rt::RasterStage::write: hipLaunchKernelGGL(rt::raster_write_kernel, g, dim3(rt::BLOCK), 0, stream, *P, *A); break;
+    case rt::RasterStage::fill:
         hipLaunchKernelGGL(rt::raster_fill_kernel, dim3((npieces + rt::BLOCK - 1) / rt::BLOCK), dim3(rt::BLOCK), 0,
                            stream, *P, *A, npieces);
-    } else {
-        if (npieces <= 0)
-            return hipSuccess;
+        break;
+    case rt::RasterStage::fill_big:
         hipLaunchKernelGGL(rt::raster_fill_big_kernel, dim3(P->max_blocks > 0 ? P->max_blocks : 1024),
                            dim3(rt::BLOCK), 0, stream, *P, *A);
+        break;
     }
     return hipGetLastError();
 }
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_raster_shade(const rt::KParams* P,
-                                                                            const rt::RasterArgs* A,
-                                                                            rt::FrameRec* fr1,
-                                                                            unsigned int* nfr1, hipStream_t stream)
+hipError_t rt_launch_raster_shade(const rt::KParams* P, const rt::RasterArgs* A, rt::FrameRec* fr1, unsigned int* nfr1,
+                                  hipStream_t stream)
 {
-    int tiles = P->tiles_x * P->tiles_y;
-    int blocks = (tiles + rt::WAVES_PER_BLOCK - 1) / rt::WAVES_PER_BLOCK;
-    if (blocks > P->max_blocks && P->max_blocks > 0)
-        blocks = P->max_blocks;
+    const int blocks = persistent_blocks(*P);
     if (blocks < 1)
         return hipSuccess;
     size_t lds = rt::lds_bytes(*P);
@@ -4158,7 +4086,7 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_raster_sha
     return hipGetLastError();
 }
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_ssao(const rt::SsaoArgs* A, hipStream_t stream)
+hipError_t rt_launch_ssao(const rt::SsaoArgs* A, hipStream_t stream)
 {
     if (A->w <= 0 || A->h <= 0)
         return hipSuccess;

@@ -1,0 +1,77 @@
+// launch.hpp -- the host-side launch wrappers kernels.hip defines and renderer.cpp calls, declared once:
+// a definition whose parameters drift from these is a compile error, not a corrupted argument.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "kparams.hpp"
+#include "ocone.hpp"
+#include "wbvh.hpp"
+
+namespace rt {
+
+// the reflection engine's passes over a chunk of frames (rt_launch_refl_stage)
+enum class ReflStage {
+    trace,     // gen + trace (refl_trace_feed_kernel with ReflArgs::feed, else refl_trace_kernel)
+    long_,     // the deferred long traces
+    pass1,     // pass1 (+ shadow list)
+    shadow,    // shadow (+ spawn)
+    resolve,
+};
+
+// the raster path's passes (rt_launch_raster_stage)
+enum class RasterStage {
+    count,
+    write,
+    fill,       // small pieces
+    fill_big,   // big pieces
+};
+
+}  // namespace rt
+
+// internal to the library: C names, hidden from its exports
+#define RT_LAUNCH extern "C" __attribute__((visibility("hidden"))) hipError_t
+
+RT_LAUNCH rt_launch_ray_trace(const rt::KParams* P, hipStream_t stream);
+RT_LAUNCH rt_launch_heavy_prep(const rt::KParams* P, uint32_t* cost, int ntiles, int32_t* list, uint32_t* bits,
+                               int32_t* ctr, int32_t* ctr_next, const unsigned long long* stats_prev,
+                               unsigned long long* stats_next, float split, int group, hipStream_t stream);
+RT_LAUNCH rt_launch_trace_rays(const rt::KParams* P, const float* o, const float* d, int n, int32_t* id, float* t,
+                               float* u, float* v, uint8_t* ret, hipStream_t stream);
+RT_LAUNCH rt_launch_wide_query(const rt::KParams* P, const float* o, const float* d, int n, int kind, float* o_out,
+                               float* d_out, int32_t* status, int32_t* id, float* t, float* u, float* v, uint8_t* sh,
+                               hipStream_t stream);
+RT_LAUNCH rt_launch_trace_colors(const rt::KParams* P, bool refl, const float* o, const float* d, int n, float4* rgba,
+                                 int32_t* src, float* t, uint8_t* found, uint8_t* shadow, hipStream_t stream);
+RT_LAUNCH rt_launch_downscale(const uint32_t* in, int w, int h_rows, int f, uint32_t* out, hipStream_t stream);
+RT_LAUNCH rt_launch_ssao(const rt::SsaoArgs* A, hipStream_t stream);
+
+// the acceleration structures
+RT_LAUNCH rt_launch_wide_gather(const rt::GTri* tris, const int32_t* slot, const uint32_t* leaf_of_slot,
+                                const int32_t* tri_id, const int32_t* tri_mat, int n, rt::GTri* wtris, uint4* wmeta,
+                                hipStream_t stream);
+RT_LAUNCH rt_launch_risk_box_init(float* B, size_t nentries, hipStream_t stream);
+RT_LAUNCH rt_launch_wide_risk(const rt::GTri* wtris, const uint4* wmeta, const rt::GNode* onodes,
+                              const rt::WNode* wnodes, const uint32_t* tri_leaf, const uint32_t* parent, uint32_t* K,
+                              float* B, unsigned long long* risk, int n, int nnodes, const rt::WRiskArgs* A,
+                              uint32_t* cap, const float* cap_dir, hipStream_t stream);
+RT_LAUNCH rt_launch_ocone(const rt::OConeEnt* E, const rt::GTri* tris, const uint32_t* todo, int n, const float lo[3],
+                          const int32_t dim[3], double h, double r, double slack, double QS, double cos_cap,
+                          uint2* cells, size_t ncells, hipStream_t stream);
+
+// the reflection engine (renderer.cpp drives the levels)
+RT_LAUNCH rt_launch_refl_level0(const rt::KParams* P, rt::FrameRec* fr1, unsigned int* nfr1, hipStream_t stream);
+RT_LAUNCH rt_launch_refl_stage(rt::ReflStage stage, const rt::KParams* P, const rt::ReflArgs* A, hipStream_t stream);
+RT_LAUNCH rt_launch_refl_keys(const rt::KParams* P, const rt::FrameRec* fr, int n, uint32_t* keys, int32_t* idx,
+                              hipStream_t stream);
+RT_LAUNCH rt_launch_refl_sort_frames(const rt::FrameRec* fr, const int32_t* order, int n, rt::FrameRec* frs,
+                                     hipStream_t stream);
+RT_LAUNCH rt_launch_refl_shadow_keys(const rt::KParams* P, const rt::SampleRec* sm, const int32_t* list, int n,
+                                     uint32_t* keys, hipStream_t stream);
+
+// the raster path
+RT_LAUNCH rt_launch_raster_stage(rt::RasterStage stage, const rt::KParams* P, const rt::RasterArgs* A, int npieces,
+                                 hipStream_t stream);
+RT_LAUNCH rt_launch_raster_shade(const rt::KParams* P, const rt::RasterArgs* A, rt::FrameRec* fr1, unsigned int* nfr1,
+                                 hipStream_t stream);

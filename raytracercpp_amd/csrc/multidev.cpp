@@ -92,7 +92,6 @@ int Renderer::set_devices(const int* ids, int n)
     auto M = std::make_unique<MultiDev>();
     M->one_device = one_device;
     M->ids.assign(ids, ids + n);
-    M->gather.device = device_;
     for (int i = 1; i < n; i++) {
         auto h = std::make_unique<Renderer>(ids[i]);
         std::string err;
@@ -100,9 +99,7 @@ int Renderer::set_devices(const int* ids, int n)
             return fail(RT_EHIP, "rt_set_devices: device " + std::to_string(ids[i]) + ": " + err);
         h->lead_ = this;   // its scene comes from this renderer's build (adopt_from_lead)
         M->helpers.push_back(std::move(h));
-        auto b = std::make_unique<DevBuf>();
-        b->device = ids[i];
-        M->bands.push_back(std::move(b));
+        M->bands.push_back(std::make_unique<DevBuf>());
     }
     if (n > 1 && !one_device) {
         std::string err;

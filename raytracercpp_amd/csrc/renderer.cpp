@@ -13,66 +13,7 @@
 #include <thread>
 
 #include "host_scene.hpp"
-
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_ray_trace(const rt::KParams* P, hipStream_t stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_heavy_prep(const rt::KParams* P, uint32_t* cost,
-                                                                                 int ntiles, int32_t* list,
-                                                                                 uint32_t* bits, int32_t* ctr,
-                                                                                 int32_t* ctr_next,
-                                                                                 const unsigned long long* stats_prev,
-                                                                                 unsigned long long* stats_next,
-                                                                                 float split, int group,
-                                                                                 hipStream_t stream);
-
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_refl_level0(const rt::KParams* P, rt::FrameRec* fr1,
-                                                                           unsigned int* nfr1, hipStream_t stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_refl_stage(int stage, const rt::KParams* P,
-                                                                          const rt::ReflArgs* A, hipStream_t stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_refl_keys(const rt::KParams* P, const rt::FrameRec* fr,
-                                                                         int n, uint32_t* keys, int32_t* idx,
-                                                                         hipStream_t stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_risk_box_init(float* B, size_t nentries,
-                                                                                    hipStream_t stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_trace_rays(const rt::KParams* P, const float* o, const float* d, int n, int32_t* id,
-                                           float* t, float* u, float* v, uint8_t* ret, hipStream_t stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_wide_query(const rt::KParams* P, const float* o,
-                                                                                 const float* d, int n, int kind,
-                                                                                 float* o_out, float* d_out,
-                                                                                 int32_t* status, int32_t* id, float* t,
-                                                                                 float* u, float* v, uint8_t* sh,
-                                                                                 hipStream_t stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_trace_colors(const rt::KParams* P, bool refl,
-                                                                                   const float* o, const float* d,
-                                                                                   int n, float4* rgba, int32_t* src,
-                                                                                   float* t, uint8_t* found,
-                                                                                   uint8_t* shadow, hipStream_t stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_raster_stage(int stage, const rt::KParams* P,
-                                                                            const rt::RasterArgs* A, int npieces,
-                                                                            hipStream_t stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_raster_shade(const rt::KParams* P,
-                                                                            const rt::RasterArgs* A,
-                                                                            rt::FrameRec* fr1, unsigned int* nfr1,
-                                                                            hipStream_t stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_ssao(const rt::SsaoArgs* A, hipStream_t stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_ocone(const rt::OConeEnt* E, const rt::GTri* tris,
-                                                                     const uint32_t* todo, int n, const float lo[3],
-                                                                     const int32_t dim[3], double h, double r, double slack,
-                                                                     double QS, double cos_cap, uint2* cells,
-                                                                     size_t ncells, hipStream_t stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_refl_shadow_keys(const rt::KParams* P, const rt::SampleRec* sm,
-                                                                                 const int32_t* list, int n, uint32_t* keys,
-                                                                                 hipStream_t stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_refl_sort_frames(const rt::FrameRec* fr, const int32_t* order,
-                                                                                int n, rt::FrameRec* frs, hipStream_t stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_wide_gather(
-    const rt::GTri* tris, const int32_t* slot, const uint32_t* leaf_of_slot, const int32_t* tri_id,
-    const int32_t* tri_mat, int n, rt::GTri* wtris, uint4* wmeta, hipStream_t stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_wide_risk(
-    const rt::GTri* wtris, const uint4* wmeta, const rt::GNode* onodes, const rt::WNode* wnodes, const uint32_t* tri_leaf,
-    const uint32_t* parent, uint32_t* K, float* B, unsigned long long* risk, int n, int nnodes, const rt::WRiskArgs* A,
-    uint32_t* cap, const float* cap_dir, hipStream_t stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t rt_launch_downscale(const uint32_t* in, int w, int h_rows, int f, uint32_t* out,
-                                          hipStream_t stream);
+#include "launch.hpp"
 
 namespace rt {
 
@@ -95,7 +36,9 @@ hipError_t DevBuf::reserve(size_t n)
     release();
     if (n == 0)
         n = 16;
-    hipError_t e = hipMalloc(&p, n);
+    hipError_t e = hipGetDevice(&device);   // the caller's device holds the buffer: release() frees under it
+    if (e == hipSuccess)
+        e = hipMalloc(&p, n);
     if (e != hipSuccess) {
         p = nullptr;
         return e;
@@ -112,6 +55,19 @@ Knobs Knobs::from_env()
         const char* v = getenv(name);
         return v ? v[0] != '0' : dflt;
     };
+    // the other variables by value: unset, the field keeps its default
+    auto flag = [](const char* name, bool dflt) {
+        const char* v = getenv(name);
+        return v ? atoi(v) != 0 : dflt;
+    };
+    auto num = [](const char* name, int dflt) {
+        const char* v = getenv(name);
+        return v ? atoi(v) : dflt;
+    };
+    auto real = [](const char* name, float dflt) {
+        const char* v = getenv(name);
+        return v ? (float)atof(v) : dflt;
+    };
     k.wbvh = on("RT_WBVH", true);   // (exact mode overrides: Renderer::fill_params)
     k.seg = on("RT_SEG", true);
     k.seg_oct = on("RT_SEG_OCTREE", false);
@@ -126,44 +82,28 @@ Knobs Knobs::from_env()
     k.exact = on("RT_EXACT", false);
     k.risk = on("RT_WBVH_RISK", true);
     k.heavy = on("RT_HEAVY_FIRST", true);
-    if (const char* v = getenv("RT_HEAVY_GROUP")) {
-        const int g = atoi(v);
-        k.heavy_group = g > 1 ? SPLIT_G : 0;   // (the split's group size is the build's, kparams.hpp RT_SPLIT_G)
-    }
-    if (const char* v = getenv("RT_HEAVY_SPLIT"))
-        k.heavy_split = std::max(0.0f, (float)atof(v));
-    if (const char* v = getenv("RT_HEAVY_SPLIT_EXP"))
-        k.heavy_split_exp = std::max(0.0f, (float)atof(v));
-    if (const char* v = getenv("RT_HEAVY_SPLIT_EXP_OVERLAP"))
-        k.heavy_split_exp_overlap = std::max(0.0f, (float)atof(v));
-    if (const char* v = getenv("RT_SPLIT_PARTS"))
-        k.split_parts = atoi(v) == 2 * SPLIT_G ? 2 * SPLIT_G : SPLIT_G;
-    if (const char* v = getenv("RT_REFL_DEFER"))   // loop iterations before a reflection query is deferred
-        k.refl_defer = std::max(0, atoi(v));
-    if (const char* v = getenv("RT_REFL_FEED"))    // lane refill of the reflection queries at this many waiting lanes
-        k.refl_feed = std::min(64, std::max(0, atoi(v)));
-    if (const char* v = getenv("RT_REFL_SAMPLE_MAJOR"))
-        k.refl_sample_major = atoi(v) != 0;
-    if (const char* v = getenv("RT_REFL_SHADOW_SORT"))
-        k.refl_shadow_sort = atoi(v) != 0;
-    if (const char* v = getenv("RT_REFL_SORTED_FRAMES"))
-        k.refl_sorted_frames = atoi(v) != 0;
-    if (const char* v = getenv("RT_RISK_CAP"))
-        k.risk_cap = atoi(v) != 0;
-    if (const char* v = getenv("RT_OCONE"))
-        k.ocone = atoi(v) != 0;
-    if (const char* v = getenv("RT_OCONE_DIM"))
-        k.ocone_dim = std::min(1024, std::max(1, atoi(v)));
-    {
-        const char* v = getenv("RT_INJECT_FRAME_FAIL");   // tests: the k-th ray_trace fails after its image start
-        k.inject_fail = v ? std::atoi(v) : 0;
-    }
+    if (getenv("RT_HEAVY_GROUP"))   // (the split's group size is the build's, kparams.hpp RT_SPLIT_G)
+        k.heavy_group = num("RT_HEAVY_GROUP", 0) > 1 ? SPLIT_G : 0;
+    k.heavy_split = std::max(0.0f, real("RT_HEAVY_SPLIT", k.heavy_split));
+    k.heavy_split_exp = std::max(0.0f, real("RT_HEAVY_SPLIT_EXP", k.heavy_split_exp));
+    k.heavy_split_exp_overlap = std::max(0.0f, real("RT_HEAVY_SPLIT_EXP_OVERLAP", k.heavy_split_exp_overlap));
+    if (getenv("RT_SPLIT_PARTS"))
+        k.split_parts = num("RT_SPLIT_PARTS", 0) == 2 * SPLIT_G ? 2 * SPLIT_G : SPLIT_G;
+    // loop iterations before a reflection query is deferred
+    k.refl_defer = std::max(0, num("RT_REFL_DEFER", k.refl_defer));
+    // lane refill of the reflection queries at this many waiting lanes
+    k.refl_feed = std::min(64, std::max(0, num("RT_REFL_FEED", k.refl_feed)));
+    k.refl_sample_major = flag("RT_REFL_SAMPLE_MAJOR", k.refl_sample_major);
+    k.refl_shadow_sort = flag("RT_REFL_SHADOW_SORT", k.refl_shadow_sort);
+    k.refl_sorted_frames = flag("RT_REFL_SORTED_FRAMES", k.refl_sorted_frames);
+    k.risk_cap = flag("RT_RISK_CAP", k.risk_cap);
+    k.ocone = flag("RT_OCONE", k.ocone);
+    k.ocone_dim = std::min(1024, std::max(1, num("RT_OCONE_DIM", k.ocone_dim)));
+    k.inject_fail = num("RT_INJECT_FRAME_FAIL", 0);   // tests: the k-th ray_trace fails after its image start
     k.async_accel = on("RT_ASYNC_ACCEL", true);
-    if (const char* ce = getenv("RT_REFL_CHUNK_LOG2")) {
-        const int v = atoi(ce);
-        if (v >= 10 && v <= 27)   // small values (tests): many chunks per level
-            k.refl_chunk_log2 = v;
-    }
+    const int chunk = num("RT_REFL_CHUNK_LOG2", k.refl_chunk_log2);
+    if (chunk >= 10 && chunk <= 27)   // small values (tests): many chunks per level
+        k.refl_chunk_log2 = chunk;
     return k;
 }
 
@@ -202,15 +142,6 @@ int Renderer::init(std::string& err)
         err = std::string("HIP init failed: ") + hipGetErrorString(e);
         return RT_EHIP;
     }
-    DevBuf* all[] = {&d_nodes_, &d_tris_,  &d_tri_id_, &d_tri_mat_, &d_tri_uv_, &d_mats_,   &d_internal_,
-                     &d_image_, &d_rgba_,  &d_hit_id_, &d_hit_t_,   &d_shadow_, &d_counters_,
-                     &d_tri9_,  &d_rcount_, &d_roff_,  &d_pieces_,  &d_piece_uv_, &d_zkey_, &d_big_, &d_scan_tmp_,
-                     &d_zbuf_,  &d_nbuf_,   &d_ao_,     &d_cones_, &d_lslab_, &d_lsin_, &d_wnodes_, &d_wtris_, &d_wmeta_, &d_wtmp_,
-                     &d_wlinks_, &d_wrisk_, &d_dbg_, &d_wnodes2_, &d_wtris2_, &d_wmeta2_, &d_wtmp2_, &d_wlinks2_,
-                     &d_ocone_, &d_ocone2_, &d_oc_ent_, &d_oc_todo_};
-    for (DevBuf* b : all) b->device = device_;
-    for (auto& b : d_tex_) b.device = device_;
-    for (auto& b : d_sky_) b.device = device_;
     return RT_OK;
 }
 
@@ -648,13 +579,13 @@ hipError_t Renderer::upload_wide(const WBvh& w, DevBuf& nodes, DevBuf& tris, Dev
     // record's triangle), the leaf of its certificate, the caller's triangle index and its material
     // (kernels.hip wide_gather_kernel)
     hipError_t e;
+    hipSetDevice(device_);
     const size_t nk = w.slot.size(), wn = w.nodes.size() * sizeof(WNode);
     const size_t nl = w.tri_leaf.size() + w.parent.size();
     if ((e = nodes.reserve(wn)) != hipSuccess || (e = tris.reserve(nk * sizeof(GTri))) != hipSuccess ||
         (e = meta.reserve(nk * 16)) != hipSuccess || (e = tmp.reserve(nk * 8)) != hipSuccess ||
         (e = links.reserve(nl * 4)) != hipSuccess)
         return e;
-    hipSetDevice(device_);
     int32_t* d_slot = tmp.as<int32_t>();
     uint32_t* d_leaf = reinterpret_cast<uint32_t*>(d_slot + nk);
     if ((e = hipMemcpyAsync(links.p, w.tri_leaf.data(), w.tri_leaf.size() * 4, hipMemcpyHostToDevice, stream)) != hipSuccess ||
@@ -1234,22 +1165,70 @@ int Renderer::launch_trace(const KParams& P, hipStream_t stream)
             return hip_fail(e, "ray_trace_kernel launch");
         return RT_OK;
     }
-    for (auto& L : refl_)
-        L.fr.device = L.ret.device = L.sm.device = L.hit.device = L.cnt.device = L.list.device = L.sort.device =
-            L.sort_tmp.device = L.res.device = L.frs.device = L.slist.device = device_;
-    size_t npx = (size_t)P.rw * P.local_rows;
+    const int rc = refl_level1_begin(P, stream);
+    if (rc != RT_OK)
+        return rc;
     ReflLevel& L1 = refl_[1];
+    if ((e = rt_launch_refl_level0(&P, L1.fr.as<FrameRec>(), L1.cnt.as<unsigned int>(), stream)) != hipSuccess)
+        return hip_fail(e, "refl_level0_kernel launch");
+    return refl_level1_finish(P, stream, "refl_level0_kernel", true);
+}
+
+// One 32-bit count of the stream's last kernels, on the host once they are done.
+hipError_t Renderer::read_u32(const void* dev, hipStream_t stream, unsigned& out)
+{
+    hipError_t e = hipMemcpyAsync(&out, dev, 4, hipMemcpyDeviceToHost, stream);
+    return e != hipSuccess ? e : hipStreamSynchronize(stream);
+}
+
+// Level 1's frames come from the launch's shading pass (refl_level0_kernel, raster_shade_kernel), at most
+// one per pixel.  Before that pass: their buffer and the zeroed count.
+int Renderer::refl_level1_begin(const KParams& P, hipStream_t stream)
+{
+    hipError_t e;
+    ReflLevel& L1 = refl_[1];
+    const size_t npx = (size_t)P.rw * P.local_rows;
     if ((e = L1.fr.reserve(npx * sizeof(FrameRec))) != hipSuccess || (e = L1.cnt.reserve(64)) != hipSuccess)
         return hip_fail(e, "hipMalloc (reflection frames)");
     if ((e = hipMemsetAsync(L1.cnt.p, 0, 4, stream)) != hipSuccess)
         return hip_fail(e, "hipMemsetAsync");
-    if ((e = rt_launch_refl_level0(&P, L1.fr.as<FrameRec>(), L1.cnt.as<unsigned int>(), stream)) != hipSuccess)
-        return hip_fail(e, "refl_level0_kernel launch");
+    return RT_OK;
+}
+
+// After it: the count (what: the pass, for the error text) and the level's passes; run_empty: refl_level runs
+// for no frames as well (launch_trace; launch_raster returns without it).
+int Renderer::refl_level1_finish(const KParams& P, hipStream_t stream, const char* what, bool run_empty)
+{
     unsigned n1 = 0;
-    if ((e = hipMemcpyAsync(&n1, L1.cnt.p, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-        (e = hipStreamSynchronize(stream)) != hipSuccess)
-        return hip_fail(e, "refl_level0_kernel");
-    return refl_level(P, 1, (int)n1, stream);
+    const hipError_t e = read_u32(refl_[1].cnt.p, stream, n1);
+    if (e != hipSuccess)
+        return hip_fail(e, what);
+    return n1 || run_empty ? refl_level(P, 1, (int)n1, stream) : RT_OK;
+}
+
+// hipcub's two-phase calls: the size query, the scratch buffer (tmp grows to it), the call itself.
+// The keys' low 30 bits sort (the Morton keys of refl_keys_kernel and refl_shadow_keys_kernel).
+static hipError_t sort_pairs(DevBuf& tmp, const uint32_t* kin, uint32_t* kout, const int32_t* vin, int32_t* vout, int n,
+                             hipStream_t stream)
+{
+    size_t tb = 0;
+    hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, n, 0, 30, stream);
+    if (e == hipSuccess)
+        e = tmp.reserve(tb);
+    if (e == hipSuccess)
+        e = hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, kin, kout, vin, vout, n, 0, 30, stream);
+    return e;
+}
+
+static hipError_t exclusive_sum(DevBuf& tmp, const int32_t* in, int32_t* out, int n, hipStream_t stream)
+{
+    size_t tb = 0;
+    hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, n, stream);
+    if (e == hipSuccess)
+        e = tmp.reserve(tb);
+    if (e == hipSuccess)
+        e = hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, in, out, n, stream);
+    return e;
 }
 
 // Frames [0, nframes) of 'level' (their samples trace at depth 'level'), in chunks;
@@ -1305,15 +1284,8 @@ int Renderer::refl_level(const KParams& P, int level, int nframes, hipStream_t s
     int32_t* idx_out = idx_in + nframes;
     if ((e = rt_launch_refl_keys(&P, L.fr.as<FrameRec>(), nframes, keys_in, idx_in, stream)) != hipSuccess)
         return hip_fail(e, "refl_keys_kernel launch");
-    {
-        size_t tb = 0;
-        if ((e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys_in, keys_out, idx_in, idx_out, nframes, 0, 30,
-                                                    stream)) != hipSuccess ||
-            (e = L.sort_tmp.reserve(tb)) != hipSuccess ||
-            (e = hipcub::DeviceRadixSort::SortPairs(L.sort_tmp.p, tb, keys_in, keys_out, idx_in, idx_out, nframes, 0,
-                                                    30, stream)) != hipSuccess)
-            return hip_fail(e, "frame sort");
-    }
+    if ((e = sort_pairs(L.sort_tmp, keys_in, keys_out, idx_in, idx_out, nframes, stream)) != hipSuccess)
+        return hip_fail(e, "frame sort");
     const int32_t* order = idx_out;
     // the frames in sorted order, copied once per level (the passes below walk the sorted positions)
     const FrameRec* frs = nullptr;
@@ -1344,7 +1316,7 @@ int Renderer::refl_level(const KParams& P, int level, int nframes, hipStream_t s
         A.stride = stride;
         A.sample_major = knobs_.refl_sample_major ? 1 : 0;
         // long queries (more than max_steps loop iterations) leave the trace kernel's waves and are
-        // traced again by stage 7 in waves of their own (the shadow list's buffer, free until pass1;
+        // traced again by ReflStage::long_ in waves of their own (the shadow list's buffer, free until pass1;
         // RT_REFL_DEFER=0: off)
         A.defer = L.list.as<int32_t>();
         A.defer_count = L.cnt.as<unsigned int>() + 2;
@@ -1353,27 +1325,20 @@ int Renderer::refl_level(const KParams& P, int level, int nframes, hipStream_t s
         A.feed = knobs_.refl_feed;
         if ((e = hipMemsetAsync(L.cnt.p, 0, 64, stream)) != hipSuccess)   // (+ the long kernel's and the feed's counters)
             return hip_fail(e, "hipMemsetAsync");
-        // trace, the deferred long traces, pass1 (+ shadow list), shadow (+ spawn)
-        static const int stages[] = {1, 7, 2, 3};
-        for (int st : stages) {
-            if (st == 3 && knobs_.refl_shadow_sort && P.compute_shadows) {
+        static const ReflStage stages[] = {ReflStage::trace, ReflStage::long_, ReflStage::pass1, ReflStage::shadow};
+        for (ReflStage st : stages) {
+            if (st == ReflStage::shadow && knobs_.refl_shadow_sort && P.compute_shadows) {
                 // the shadow list sorted by hit point (Morton order): the shadow pass's adjacent lanes start
                 // from nearby points (its entries' results do not depend on their order)
                 unsigned n = 0;
-                if ((e = hipMemcpyAsync(&n, A.list_count, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-                    (e = hipStreamSynchronize(stream)) != hipSuccess)
+                if ((e = read_u32(A.list_count, stream, n)) != hipSuccess)
                     return hip_fail(e, "shadow list count");
                 if (n > 1) {
                     uint32_t* kin = L.slist.as<uint32_t>();
                     uint32_t* kout = kin + n;
                     int32_t* vout = reinterpret_cast<int32_t*>(kout + n);
-                    size_t tb = 0;
                     if ((e = rt_launch_refl_shadow_keys(&P, A.sm, A.list, (int)n, kin, stream)) != hipSuccess ||
-                        (e = hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, A.list, vout, (int)n, 0, 30,
-                                                                stream)) != hipSuccess ||
-                        (e = L.sort_tmp.reserve(tb)) != hipSuccess ||
-                        (e = hipcub::DeviceRadixSort::SortPairs(L.sort_tmp.p, tb, kin, kout, A.list, vout, (int)n, 0, 30,
-                                                                stream)) != hipSuccess)
+                        (e = sort_pairs(L.sort_tmp, kin, kout, A.list, vout, (int)n, stream)) != hipSuccess)
                         return hip_fail(e, "shadow list sort");
                     A.list = vout;
                 }
@@ -1382,15 +1347,14 @@ int Renderer::refl_level(const KParams& P, int level, int nframes, hipStream_t s
                 return hip_fail(e, "reflection stage launch");
         }
         unsigned nchild = 0;
-        if ((e = hipMemcpyAsync(&nchild, L.cnt.p, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-            (e = hipStreamSynchronize(stream)) != hipSuccess)
+        if ((e = read_u32(L.cnt.p, stream, nchild)) != hipSuccess)
             return hip_fail(e, "reflection stages");
         if (nchild > 0) {
             int rc = refl_level(P, level + 1, (int)nchild, stream);
             if (rc != RT_OK)
                 return rc;
         }
-        if ((e = rt_launch_refl_stage(5, &P, &A, stream)) != hipSuccess)
+        if ((e = rt_launch_refl_stage(ReflStage::resolve, &P, &A, stream)) != hipSuccess)
             return hip_fail(e, "refl_resolve_kernel launch");
     }
     return RT_OK;
@@ -1425,18 +1389,13 @@ int Renderer::launch_raster(const KParams& P, hipStream_t stream)
     A.count = d_rcount_.as<int32_t>();
     A.offset = d_roff_.as<int32_t>();
     if ((e = hipMemsetAsync(A.count, 0, (size_t)(n + 1) * 4, stream)) != hipSuccess) return hip_fail(e, "hipMemsetAsync");
-    if ((e = rt_launch_raster_stage(0, &P, &A, 0, stream)) != hipSuccess) return hip_fail(e, "raster_count_kernel launch");
-    size_t tb = 0;
-    if ((e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, A.count, d_roff_.as<int32_t>(), (int)(n + 1), stream)) !=
-            hipSuccess ||
-        (e = d_scan_tmp_.reserve(tb)) != hipSuccess ||
-        (e = hipcub::DeviceScan::ExclusiveSum(d_scan_tmp_.p, tb, A.count, d_roff_.as<int32_t>(), (int)(n + 1),
-                                              stream)) != hipSuccess)
+    if ((e = rt_launch_raster_stage(RasterStage::count, &P, &A, 0, stream)) != hipSuccess) return hip_fail(e, "raster_count_kernel launch");
+    if ((e = exclusive_sum(d_scan_tmp_, A.count, d_roff_.as<int32_t>(), (int)(n + 1), stream)) != hipSuccess)
         return hip_fail(e, "piece scan");
-    int32_t npieces = 0;
-    if ((e = hipMemcpyAsync(&npieces, d_roff_.as<int32_t>() + n, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-        (e = hipStreamSynchronize(stream)) != hipSuccess)
+    unsigned total = 0;
+    if ((e = read_u32(d_roff_.as<int32_t>() + n, stream, total)) != hipSuccess)
         return hip_fail(e, "raster_count_kernel");
+    const int32_t npieces = (int32_t)total;
     size_t npx = (size_t)P.rw * P.local_rows;
     if ((e = d_pieces_.reserve((size_t)npieces * sizeof(RasterPiece))) != hipSuccess ||
         (e = d_piece_uv_.reserve((size_t)npieces * 24)) != hipSuccess ||
@@ -1450,33 +1409,26 @@ int Renderer::launch_raster(const KParams& P, hipStream_t stream)
     if ((e = hipMemsetAsync(A.zkey, 0xff, npx * 8, stream)) != hipSuccess ||
         (e = hipMemsetAsync(A.nbig, 0, 4, stream)) != hipSuccess)
         return hip_fail(e, "hipMemsetAsync");
-    for (int stage = 1; stage <= 3; stage++)
+    for (RasterStage stage : {RasterStage::write, RasterStage::fill, RasterStage::fill_big})
         if ((e = rt_launch_raster_stage(stage, &P, &A, npieces, stream)) != hipSuccess)
             return hip_fail(e, "raster kernel launch");
     // shading reads texcoords through Rec::tri = piece index: the piece table stands in
     // for tri_uv (trace_triangle's temporary Triangle carries the clipped texcoords)
     KParams PS = P;
     PS.tri_uv = A.piece_uv;
-    for (auto& L : refl_)
-        L.fr.device = L.ret.device = L.sm.device = L.hit.device = L.cnt.device = L.list.device = L.sort.device =
-            L.sort_tmp.device = L.res.device = L.frs.device = L.slist.device = device_;
     ReflLevel& L1 = refl_[1];
     const bool frames = P.has_reflection;
     if (frames) {
-        if ((e = L1.fr.reserve(npx * sizeof(FrameRec))) != hipSuccess || (e = L1.cnt.reserve(64)) != hipSuccess)
-            return hip_fail(e, "hipMalloc (reflection frames)");
-        if ((e = hipMemsetAsync(L1.cnt.p, 0, 4, stream)) != hipSuccess) return hip_fail(e, "hipMemsetAsync");
+        const int rc = refl_level1_begin(P, stream);
+        if (rc != RT_OK)
+            return rc;
     }
     if ((e = rt_launch_raster_shade(&PS, &A, frames ? L1.fr.as<FrameRec>() : nullptr,
                                     frames ? L1.cnt.as<unsigned int>() : nullptr, stream)) != hipSuccess)
         return hip_fail(e, "raster_shade_kernel launch");
     if (!frames)
         return RT_OK;
-    unsigned n1 = 0;
-    if ((e = hipMemcpyAsync(&n1, L1.cnt.p, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
-        (e = hipStreamSynchronize(stream)) != hipSuccess)
-        return hip_fail(e, "raster_shade_kernel");
-    return n1 ? refl_level(P, 1, (int)n1, stream) : RT_OK;
+    return refl_level1_finish(P, stream, "raster_shade_kernel", false);   // (no frames: nothing to run)
 }
 
 // the checks ray_trace / raster_trace / render_bands_device make before a launch
@@ -2009,7 +1961,6 @@ int Renderer::render_bands_impl(int band_rows, int rank, int nranks, const int32
     if (si < 0) {
         if (band_nslots_ < BAND_SLOTS) {
             si = band_nslots_++;
-            band_slot_[si].counters.device = band_slot_[si].tmp.device = device_;
             if ((e = hipEventCreateWithFlags(&band_slot_[si].done, hipEventDisableTiming)) != hipSuccess ||
                 (e = hipEventCreateWithFlags(&band_slot_[si].mark, hipEventDisableTiming)) != hipSuccess)
                 return hip_fail(e, "hipEventCreate");
@@ -2050,7 +2001,6 @@ int Renderer::render_bands_impl(int band_rows, int rank, int nranks, const int32
         if (host != S.map_host || nb != S.map_nb) {
             if (S.live && (e = hipEventSynchronize(S.done)) != hipSuccess)
                 return hip_fail(e, "render_band_list_device: waiting for the slot's last launch");
-            S.map.device = device_;
             if ((e = S.map.reserve(host.size() * 4)) != hipSuccess ||
                 (e = hipMemcpy(S.map.p, host.data(), host.size() * 4, hipMemcpyHostToDevice)) != hipSuccess)
                 return hip_fail(e, "band list upload");
@@ -2216,7 +2166,6 @@ int Renderer::prepare_heavy(KParams& P, TileCost& T, hipStream_t stream, uint64_
     const int ntiles = P.tiles_x * P.tiles_y;
     if (ntiles <= 0)
         return RT_OK;
-    T.cost.device = T.heavy.device = device_;
     const size_t nb = ((size_t)ntiles + 31) / 32;
     hipError_t e;
     // T.heavy: the list (ntiles), the bits (nb words), then two {sum, max} pairs of the launches' tile
@@ -2316,7 +2265,6 @@ int Renderer::trace_rays(const float* orig, const float* dir, int64_t n, int32_t
     KParams P;
     fill_params(P);
     DevBuf din, dout;
-    din.device = dout.device = device_;
     size_t nb = (size_t)n;
     hipError_t e;
     if ((e = din.reserve(nb * 24)) != hipSuccess || (e = dout.reserve(nb * 17)) != hipSuccess)
@@ -2362,7 +2310,6 @@ int Renderer::wide_query(const float* orig, const float* dir, int64_t n, int kin
     KParams P;
     fill_params(P);
     DevBuf din, dout;
-    din.device = dout.device = device_;
     const size_t nb = (size_t)n;
     hipError_t e;
     // outputs: o, d (12 B each), status, id, t, u, v (4 B each), shadowed (1 B) per ray
@@ -2500,7 +2447,6 @@ int Renderer::trace_ray_colors(const float* orig, const float* dir, int64_t n, i
     fill_params(P);
     P.max_recursion_depth = s_.max_recursion_depth - depth;   // only the difference is read
     DevBuf din, dout;
-    din.device = dout.device = device_;
     size_t nb = (size_t)n;
     hipError_t e;
     if ((e = din.reserve(nb * 24)) != hipSuccess || (e = dout.reserve(nb * 26)) != hipSuccess ||

@@ -25,10 +25,10 @@ namespace rt {
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
-    int device = 0;
+    int device = 0;   // the device that holds p: the calling thread's when reserve allocated it
     ~DevBuf();
     hipError_t reserve(size_t n);   // grows (never shrinks); contents undefined after growth
-    void release();
+    void release();                 // frees under 'device' (the calling thread's current device afterwards)
     template <class T> T* as() const { return static_cast<T*>(p); }
     // exchanges the allocations (a copy would free one buffer twice)
     void swap(DevBuf& o)
@@ -213,6 +213,10 @@ private:
     int launch_ssao();
     int trace_frame();
     int refl_level(const KParams& P, int level, int nframes, hipStream_t stream);
+    // level 1 around the launch's shading pass: its frame buffer and zeroed count, then the count and refl_level
+    int refl_level1_begin(const KParams& P, hipStream_t stream);
+    int refl_level1_finish(const KParams& P, hipStream_t stream, const char* what, bool run_empty);
+    static hipError_t read_u32(const void* dev, hipStream_t stream, unsigned& out);
     // frames in flight (render_bands_device): make 'stream' wait for every live slot's last
     // launch, or the host for all of them (before buffers that launches read are replaced)
     int wait_slots(hipStream_t stream);
