@@ -150,6 +150,25 @@ int rt_set_exact(rt_renderer *r, int on);
  * quick tree). */
 int rt_finish_accel(rt_renderer *r);
 
+/* Device octree build (no reference counterpart).  on != 0: after a geometry change
+ * the octree is built on the GPU into the tables the frames read, and copied back for the host-side
+ * structures built from it; the flattened arrays are byte for byte the host build's, so every frame
+ * is the same.  Off (default): the host build.  Inputs the device builder does not take
+ * (bvh_max_depth outside 0..30, more than 2^26 triangles) build on the host as before; brute-force
+ * mode (enable_bvh off) never uses it.  Also RT_GPU_BUILD=1 at rt_create.
+ * rt_get_device_builds: device octree builds since rt_create (rt_stats host_builds counts only the
+ * host's). */
+int rt_set_device_build(rt_renderer *r, int on);
+int rt_get_device_builds(rt_renderer *r, int64_t *count);
+
+/* The device builder alone: uploads tri9 ([n][9] world-space vertices) to 'device', builds and
+ * flattens the octree there, copies the arrays back and returns rt_octree_digest's digest and
+ * stats[7] (rt_mi355x_diag.h) of them.  ms (optional) = {the device build by HIP events, the whole
+ * call on the host clock}.  RT_EUNSUPPORTED for an input the builder does not take (as above, or
+ * a non-finite coordinate); RT_EHIP (rt_last_error) without a usable device. */
+int rt_octree_build_device(int32_t device, const float *tri9, int64_t n, int32_t max_depth, int32_t leaf_max_obj_count,
+                           uint64_t *digest, int64_t stats[7], float ms[2]);
+
 /* Single-process multi-device rendering (no reference counterpart: the reference renders on
  * one host, RenderThread::run, QT/mainWindowThreads.cpp:39-65).  ids[0] must be the handle's
  * device; n = 0 (or ids NULL) returns to one device.  rt_render then renders on every device

@@ -138,6 +138,10 @@ SIGNATURES = {
     "rt_obj_close": (None, [_H]),
     "rt_octree_digest": (C.c_int, [_f32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), _i64p,
                                    _f32p]),
+    "rt_octree_build_device": (C.c_int, [C.c_int32, _f32p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_uint64),
+                                         _i64p, _f32p]),
+    "rt_set_device_build": (C.c_int, [_H, C.c_int]),
+    "rt_get_device_builds": (C.c_int, [_H, _i64p]),
     "rt_debug_read": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_int64]),
     "rt_tile_costs": (C.c_int, [_H, C.POINTER(C.c_uint32), C.c_int64, _i32p, _i32p]),
     "rt_wbvh_query": (C.c_int, [_f32p, C.c_int64, C.c_int32, C.c_int32, _f32p, _f32p, C.c_int64, _i32p, _i32p, _f32p,
@@ -350,3 +354,17 @@ def octree_digest(tri9, max_depth=12, leaf=40, builder=0):
                                  ptr(st, _i64p), C.byref(ms)), "rt_octree_digest")
     keys = ("inner", "leaves", "empty_leaves", "max_leaf", "max_depth", "nodes", "levels")
     return int(dg.value), dict(zip(keys, map(int, st))), float(ms.value)
+
+
+def octree_build_device(tri9, max_depth=12, leaf=40, device=0):
+    """rt_octree_build_device: (digest, stats dict, (device build ms, whole call ms)) of the octree built on
+    the GPU, digested as octree_digest does.  Raises RtError (RT_EUNSUPPORTED: the builder does not take the
+    input; RT_EHIP: no usable device)."""
+    tri9 = f32(tri9).reshape(-1, 9)
+    dg = C.c_uint64()
+    st = np.zeros(7, np.int64)
+    ms = np.zeros(2, np.float32)
+    check(lib().rt_octree_build_device(device, ptr(tri9, _f32p), tri9.shape[0], max_depth, leaf, C.byref(dg),
+                                       ptr(st, _i64p), ptr(ms, _f32p)), "rt_octree_build_device")
+    keys = ("inner", "leaves", "empty_leaves", "max_leaf", "max_depth", "nodes", "levels")
+    return int(dg.value), dict(zip(keys, map(int, st))), (float(ms[0]), float(ms[1]))

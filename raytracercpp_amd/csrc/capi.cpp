@@ -10,6 +10,7 @@
 #include "../../include/rt_mi355x_diag.h"   // (includes rt_mi355x.h)
 #include "host_scene.hpp"
 #include "octree.hpp"
+#include "octree_gpu.hpp"
 #include "ocone.hpp"
 #include "wbvh.hpp"
 #include "renderer.hpp"
@@ -47,6 +48,34 @@ int guarded(rt::Renderer* r, F&& f)
 }
 
 rt::Renderer* R(rt_renderer* r) { return reinterpret_cast<rt::Renderer*>(r); }
+
+// rt_octree_digest / rt_octree_build_device: the 64-bit FNV-1a digest of a flattened octree's
+// nodes, triangle records, slot map and level count, and its stats[7]
+void octree_report(const rt::FlatOctree& f, uint64_t* digest, int64_t* stats)
+{
+    uint64_t h = 1469598103934665603ull;
+    auto mix = [&h](const void* p, size_t len) {
+        const unsigned char* b = static_cast<const unsigned char*>(p);
+        for (size_t i = 0; i < len; i++) {
+            h ^= b[i];
+            h *= 1099511628211ull;
+        }
+    };
+    mix(f.nodes.data(), f.nodes.size() * sizeof(rt::GNode));
+    mix(f.tris.data(), f.tris.size() * sizeof(rt::GTri));
+    mix(f.tri_id.data(), f.tri_id.size() * sizeof(int32_t));
+    mix(&f.levels, sizeof(f.levels));
+    *digest = h;
+    if (stats) {
+        stats[0] = f.stats.inner;
+        stats[1] = f.stats.leaves;
+        stats[2] = f.stats.empty_leaves;
+        stats[3] = f.stats.max_leaf;
+        stats[4] = f.stats.max_depth;
+        stats[5] = f.stats.nodes;
+        stats[6] = f.levels;
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -658,33 +687,111 @@ int rt_octree_digest(const float* tri9, int64_t n, int32_t max_depth, int32_t le
             rt::build_flat_octree(tri9, n, max_depth, leaf_max_obj_count, f);
         if (ms)
             *ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        uint64_t h = 1469598103934665603ull;
-        auto mix = [&h](const void* p, size_t len) {
-            const unsigned char* b = static_cast<const unsigned char*>(p);
-            for (size_t i = 0; i < len; i++) {
-                h ^= b[i];
-                h *= 1099511628211ull;
-            }
-        };
-        mix(f.nodes.data(), f.nodes.size() * sizeof(rt::GNode));
-        mix(f.tris.data(), f.tris.size() * sizeof(rt::GTri));
-        mix(f.tri_id.data(), f.tri_id.size() * sizeof(int32_t));
-        mix(&f.levels, sizeof(f.levels));
-        *digest = h;
-        if (stats) {
-            stats[0] = f.stats.inner;
-            stats[1] = f.stats.leaves;
-            stats[2] = f.stats.empty_leaves;
-            stats[3] = f.stats.max_leaf;
-            stats[4] = f.stats.max_depth;
-            stats[5] = f.stats.nodes;
-            stats[6] = f.levels;
-        }
+        octree_report(f, digest, stats);
         return RT_OK;
     } catch (const std::bad_alloc&) {
         g_err = "rt_octree_digest: out of host memory";
         return RT_ENOMEM;
     }
+}
+
+int rt_octree_build_device(int32_t device, const float* tri9, int64_t n, int32_t max_depth, int32_t leaf_max_obj_count,
+                           uint64_t* digest, int64_t stats[7], float ms[2])
+{
+    if (n < 0 || (n > 0 && !tri9) || !digest)
+        return bad("rt_octree_build_device: bad arguments");
+    auto t0 = std::chrono::steady_clock::now();
+    bool finite = true;   // (the renderer rejects such geometry before any build)
+    for (int64_t i = 0; i < 9 * n && finite; i++) finite = std::isfinite(tri9[i]);
+    if (!rt::octree_device_supported(n, max_depth) || !finite) {
+        g_err = "rt_octree_build_device: input outside the device builder's range";
+        return RT_EUNSUPPORTED;
+    }
+    auto hip_bad = [](hipError_t e, const char* what) {
+        g_err = std::string("rt_octree_build_device: ") + what + ": " + hipGetErrorString(e);
+        return RT_EHIP;
+    };
+    try {
+        hipError_t e = hipSetDevice(device);
+        if (e != hipSuccess)
+            return hip_bad(e, "hipSetDevice");
+        rt::OctreeGpuScratch scratch;
+        rt::DevBuf d_tri9, d_nodes, d_tris, d_tri_id, d_info;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        struct EvGuard {
+            hipEvent_t* ev;
+            ~EvGuard()
+            {
+                for (int i = 0; i < 2; i++)
+                    if (ev[i]) (void)hipEventDestroy(ev[i]);
+            }
+        } guard{ev};
+        if ((e = d_tri9.reserve((size_t)n * 36)) != hipSuccess || (e = d_info.reserve(sizeof(rt::OctreeDevInfo))) != hipSuccess ||
+            (e = hipEventCreate(&ev[0])) != hipSuccess || (e = hipEventCreate(&ev[1])) != hipSuccess)
+            return hip_bad(e, "allocation");
+        if (n > 0 && (e = hipMemcpy(d_tri9.p, tri9, (size_t)n * 36, hipMemcpyHostToDevice)) != hipSuccess)
+            return hip_bad(e, "upload");
+        rt::OctreeDevInfo info;
+        if ((e = hipEventRecord(ev[0], nullptr)) != hipSuccess)
+            return hip_bad(e, "hipEventRecord");
+        int rc = rt::build_flat_octree_device(scratch, d_tri9.as<float>(), n, max_depth, leaf_max_obj_count, d_nodes,
+                                              d_tris, d_tri_id, d_info.as<rt::OctreeDevInfo>(), &info, nullptr, &e);
+        if (rc == rt::OCT_GPU_UNSUPPORTED) {
+            g_err = "rt_octree_build_device: input outside the device builder's range";
+            return RT_EUNSUPPORTED;
+        }
+        if (rc != rt::OCT_GPU_OK)
+            return hip_bad(e, "build");
+        float dev_ms = 0.0f;
+        if ((e = hipEventRecord(ev[1], nullptr)) != hipSuccess || (e = hipEventSynchronize(ev[1])) != hipSuccess ||
+            (e = hipEventElapsedTime(&dev_ms, ev[0], ev[1])) != hipSuccess)
+            return hip_bad(e, "timing");
+        rt::FlatOctree f;
+        f.nodes.resize((size_t)info.nodes);
+        f.tris.resize((size_t)info.tris);
+        f.tri_id.resize((size_t)info.tris);
+        f.levels = info.levels;
+        f.ordered_slabs = info.ordered_slabs != 0;
+        f.stats.inner = info.stats[0];
+        f.stats.leaves = info.stats[1];
+        f.stats.empty_leaves = info.stats[2];
+        f.stats.max_leaf = info.stats[3];
+        f.stats.max_depth = info.stats[4];
+        f.stats.nodes = info.stats[5];
+        if (info.nodes &&
+            (e = hipMemcpy(f.nodes.data(), d_nodes.p, f.nodes.size() * sizeof(rt::GNode), hipMemcpyDeviceToHost)) != hipSuccess)
+            return hip_bad(e, "readback");
+        if (info.tris &&
+            ((e = hipMemcpy(f.tris.data(), d_tris.p, f.tris.size() * sizeof(rt::GTri), hipMemcpyDeviceToHost)) != hipSuccess ||
+             (e = hipMemcpy(f.tri_id.data(), d_tri_id.p, f.tri_id.size() * 4, hipMemcpyDeviceToHost)) != hipSuccess))
+            return hip_bad(e, "readback");
+        octree_report(f, digest, stats);
+        if (ms) {
+            ms[0] = dev_ms;
+            ms[1] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+        return RT_OK;
+    } catch (const std::bad_alloc&) {
+        g_err = "rt_octree_build_device: out of host memory";
+        return RT_ENOMEM;
+    }
+}
+
+int rt_set_device_build(rt_renderer* r, int on)
+{
+    return guarded(R(r), [&] {
+        R(r)->set_device_build(on != 0);
+        return RT_OK;
+    });
+}
+int rt_get_device_builds(rt_renderer* r, int64_t* count)
+{
+    return guarded(R(r), [&] {
+        if (!count)
+            return RT_EINVAL;
+        *count = R(r)->device_builds();
+        return RT_OK;
+    });
 }
 
 #if defined(W_DIAG) && !defined(__HIP_DEVICE_COMPILE__)

@@ -14,6 +14,7 @@
 
 #include "host_scene.hpp"
 #include "launch.hpp"
+#include "octree_gpu.hpp"
 
 namespace rt {
 
@@ -101,6 +102,7 @@ Knobs Knobs::from_env()
     k.ocone_dim = std::min(1024, std::max(1, num("RT_OCONE_DIM", k.ocone_dim)));
     k.inject_fail = num("RT_INJECT_FRAME_FAIL", 0);   // tests: the k-th ray_trace fails after its image start
     k.async_accel = on("RT_ASYNC_ACCEL", true);
+    k.gpu_build = flag("RT_GPU_BUILD", k.gpu_build);
     const int chunk = num("RT_REFL_CHUNK_LOG2", k.refl_chunk_log2);
     if (chunk >= 10 && chunk <= 27)   // small values (tests): many chunks per level
         k.refl_chunk_log2 = chunk;
@@ -167,6 +169,7 @@ Renderer::~Renderer()
         if (ev) hipEventDestroy(ev);
     if (display_stream_) hipStreamDestroy(display_stream_);
     if (display_host_) hipHostFree(display_host_);
+    if (build_pin_) hipHostFree(build_pin_);
     for (void* q : display_old_)
         hipHostFree(q);
 }
@@ -201,8 +204,10 @@ int Renderer::set_settings(const rt_settings& s)
 {
     if (s.image_width <= 0 || s.image_height <= 0 || (s.enable_ssaa && s.ssaa_factor <= 0))
         return fail(RT_EINVAL, "invalid image size / ssaa_factor");
-    if (s.bvh_max_depth > 30)
-        return fail(RT_EUNSUPPORTED, "bvh_max_depth > 30");
+    // (31: a tree that does reach 32 levels is refused when it is built, ensure_device_scene; the device
+    // builder takes 0 .. 30 and leaves 31 to the host)
+    if (s.bvh_max_depth > 31)
+        return fail(RT_EUNSUPPORTED, "bvh_max_depth > 31");
     bool bvh_changed = s.enable_bvh != s_.enable_bvh || s.bvh_max_depth != s_.bvh_max_depth ||
                        s.bvh_leaf_object_count != s_.bvh_leaf_object_count;
     s_ = s;
@@ -839,6 +844,125 @@ int Renderer::adopt_from_lead()
     return RT_OK;
 }
 
+// The octree by the device builder (octree_gpu.hpp): tri_ goes up through the pinned staging buffer,
+// the builder writes d_nodes_ / d_tris_ / d_tri_id_ in place, and the three arrays come back into oct_
+// (the quick wide BVH, the leaf cones and the background build read them on the host) in chunks, the
+// DMA of one chunk beside the host's copy of the one before.
+int Renderer::build_octree_device(int64_t n, bool& built)
+{
+    built = false;
+    if (!octree_device_supported(n, s_.bvh_max_depth))
+        return RT_OK;
+    hipError_t e = hipSuccess;
+    auto pin = [&](size_t bytes) {
+        if (bytes <= build_pin_bytes_)
+            return hipSuccess;
+        if (build_pin_)
+            (void)hipHostFree(build_pin_);
+        build_pin_ = nullptr;
+        build_pin_bytes_ = 0;
+        hipError_t pe = hipHostMalloc(&build_pin_, bytes, hipHostMallocDefault);
+        if (pe == hipSuccess)
+            build_pin_bytes_ = bytes;
+        else
+            build_pin_ = nullptr;
+        return pe;
+    };
+    constexpr size_t CHUNK = 4u << 20;
+    constexpr int RING = 4;
+    const size_t in_bytes = (size_t)n * 9 * 4;
+    if (!oct_gpu_)
+        oct_gpu_ = std::make_unique<OctreeGpuScratch>();
+    if ((e = pin(RING * CHUNK)) != hipSuccess || (e = d_tri9_.reserve(in_bytes)) != hipSuccess ||
+        (e = d_oct_info_.reserve(sizeof(OctreeDevInfo))) != hipSuccess)
+        return hip_fail(e, "hipMalloc (device octree build)");
+    tri9_dirty_ = true;   // (the raster path uploads its own copy)
+    char* ring = static_cast<char*>(build_pin_);
+    hipEvent_t ev[RING] = {};
+    struct EvGuard {
+        hipEvent_t* ev;
+        ~EvGuard()
+        {
+            for (int i = 0; i < RING; i++)
+                if (ev[i]) (void)hipEventDestroy(ev[i]);
+        }
+    } guard{ev};
+    for (int i = 0; i < RING && e == hipSuccess; i++) e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
+    // staging: the host fills one chunk of the ring while the DMA takes the one before
+    const char* src = reinterpret_cast<const char*>(tri_.data());
+    for (size_t i = 0, off = 0; e == hipSuccess && off < in_bytes; i++, off += CHUNK) {
+        const size_t len = std::min(CHUNK, in_bytes - off);
+        if (i >= RING)
+            e = hipEventSynchronize(ev[i % RING]);   // the slot's last upload has left it
+        if (e == hipSuccess) {
+            std::memcpy(ring + (i % RING) * CHUNK, src + off, len);
+            e = hipMemcpyAsync(d_tri9_.as<char>() + off, ring + (i % RING) * CHUNK, len, hipMemcpyHostToDevice, stream_);
+        }
+        if (e == hipSuccess)
+            e = hipEventRecord(ev[i % RING], stream_);
+    }
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(stream_);
+        return hip_fail(e, "upload (device octree build)");
+    }
+    OctreeDevInfo info;
+    int rc = build_flat_octree_device(*oct_gpu_, d_tri9_.as<float>(), n, s_.bvh_max_depth, s_.bvh_leaf_object_count,
+                                      d_nodes_, d_tris_, d_tri_id_, d_oct_info_.as<OctreeDevInfo>(), &info, stream_,
+                                      &e);
+    if (rc == OCT_GPU_UNSUPPORTED)
+        return RT_OK;
+    if (rc != OCT_GPU_OK)
+        return hip_fail(e, "device octree build");
+    // (oct_'s arrays keep their allocations from build to build: no fresh pages to fault in)
+    oct_.nodes.resize((size_t)info.nodes);
+    oct_.tris.resize((size_t)info.tris);
+    oct_.tri_id.resize((size_t)info.tris);
+    oct_.levels = info.levels;
+    oct_.ordered_slabs = info.ordered_slabs != 0;
+    oct_.stats.inner = info.stats[0];
+    oct_.stats.leaves = info.stats[1];
+    oct_.stats.empty_leaves = info.stats[2];
+    oct_.stats.max_leaf = info.stats[3];
+    oct_.stats.max_depth = info.stats[4];
+    oct_.stats.nodes = info.stats[5];
+    // readback: a ring of pinned chunks, each copied out once its event has passed
+    struct Part {
+        char* dst;
+        const char* src;
+        size_t bytes;
+    } parts[3] = {{reinterpret_cast<char*>(oct_.nodes.data()), d_nodes_.as<char>(), oct_.nodes.size() * sizeof(GNode)},
+                  {reinterpret_cast<char*>(oct_.tris.data()), d_tris_.as<char>(), oct_.tris.size() * sizeof(GTri)},
+                  {reinterpret_cast<char*>(oct_.tri_id.data()), d_tri_id_.as<char>(), oct_.tri_id.size() * 4}};
+    struct Piece {
+        char* dst;
+        const char* src;
+        size_t bytes;
+    };
+    std::vector<Piece> pieces;
+    for (const Part& p : parts)
+        for (size_t off = 0; off < p.bytes; off += CHUNK)
+            pieces.push_back({p.dst + off, p.src + off, std::min(CHUNK, p.bytes - off)});
+    const size_t np = pieces.size();
+    for (size_t i = 0; e == hipSuccess && i < np + RING; i++) {
+        if (i >= RING) {   // piece i - RING has landed in the slot piece i takes next
+            const Piece& q = pieces[i - RING];
+            if ((e = hipEventSynchronize(ev[i % RING])) == hipSuccess)
+                std::memcpy(q.dst, ring + (i % RING) * CHUNK, q.bytes);
+        }
+        if (e == hipSuccess && i < np) {
+            e = hipMemcpyAsync(ring + (i % RING) * CHUNK, pieces[i].src, pieces[i].bytes, hipMemcpyDeviceToHost, stream_);
+            if (e == hipSuccess)
+                e = hipEventRecord(ev[i % RING], stream_);
+        }
+    }
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(stream_);
+        return hip_fail(e, "readback (device octree build)");
+    }
+    built = true;
+    return RT_OK;
+}
+
 int Renderer::ensure_device_scene()
 {
     hipError_t e = hipSetDevice(device_);
@@ -862,8 +986,15 @@ int Renderer::ensure_device_scene()
         for (float c : tri_)
             if (!std::isfinite(c))
                 return fail(RT_EINVAL, "triangle with a non-finite vertex coordinate");
+        bool dev_built = false;
         if (s_.enable_bvh) {
-            build_flat_octree(tri_.data(), n, s_.bvh_max_depth, s_.bvh_leaf_object_count, oct_);
+            if (knobs_.gpu_build && n > 0) {
+                int rc = build_octree_device(n, dev_built);
+                if (rc != RT_OK)
+                    return rc;
+            }
+            if (!dev_built)
+                build_flat_octree(tri_.data(), n, s_.bvh_max_depth, s_.bvh_leaf_object_count, oct_);
             if (oct_.levels > 31)
                 return fail(RT_EUNSUPPORTED, "octree deeper than 31 levels");
             if (!oct_.ordered_slabs)
@@ -885,8 +1016,8 @@ int Renderer::ensure_device_scene()
                 oct_.tri_id[(size_t)i] = (int32_t)i;
             }
         }
-        build_split_ms_[0] = ms_since(t0);
-        ++host_builds_;
+        build_split_ms_[0] = ms_since(t0);   // (a device build: with its readback)
+        ++(dev_built ? device_builds_ : host_builds_);
         oct_nn_ = (int64_t)oct_.nodes.size();
         oct_nt_ = (int64_t)oct_.tris.size();
         oct_levels_ = oct_.levels;
@@ -902,9 +1033,11 @@ int Renderer::ensure_device_scene()
             (e = d_tri_uv_.reserve(tri_uv_.size() * 4)) != hipSuccess)
             return hip_fail(e, "hipMalloc (scene)");
         hipSetDevice(device_);
-        if (nb) e = hipMemcpyAsync(d_nodes_.p, oct_.nodes.data(), nb, hipMemcpyHostToDevice, stream_);
-        if (e == hipSuccess && tb) e = hipMemcpyAsync(d_tris_.p, oct_.tris.data(), tb, hipMemcpyHostToDevice, stream_);
-        if (e == hipSuccess && !oct_.tri_id.empty())
+        // (a device build wrote the three octree tables in place)
+        if (nb && !dev_built) e = hipMemcpyAsync(d_nodes_.p, oct_.nodes.data(), nb, hipMemcpyHostToDevice, stream_);
+        if (e == hipSuccess && tb && !dev_built)
+            e = hipMemcpyAsync(d_tris_.p, oct_.tris.data(), tb, hipMemcpyHostToDevice, stream_);
+        if (e == hipSuccess && !oct_.tri_id.empty() && !dev_built)
             e = hipMemcpyAsync(d_tri_id_.p, oct_.tri_id.data(), oct_.tri_id.size() * 4, hipMemcpyHostToDevice, stream_);
         if (e == hipSuccess && !tri_mat_.empty())
             e = hipMemcpyAsync(d_tri_mat_.p, tri_mat_.data(), tri_mat_.size() * 4, hipMemcpyHostToDevice, stream_);

@@ -22,6 +22,8 @@
 
 namespace rt {
 
+struct OctreeGpuScratch;   // octree_gpu.hpp
+
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
@@ -89,6 +91,8 @@ struct Knobs {
     bool ocone = true;        // RT_OCONE=0: no origin cones (reflection queries always run case (b), ocone.hpp)
     int ocone_dim = 128;      // RT_OCONE_DIM=n: the origin-cone grid's cells along the scene's longest axis
     int inject_fail = 0;      // RT_INJECT_FRAME_FAIL=k (tests): the k-th ray_trace fails after its image start
+    bool gpu_build = false;   // RT_GPU_BUILD=1 / rt_set_device_build: the octree is built on the device
+                              // (octree_gpu.hpp; the same bytes as the host build)
     bool async_accel = true;  // RT_ASYNC_ACCEL=0: the leaf cones / slabs and the wide BVH are built
                               // before the first frame instead of beside it
     static Knobs from_env();
@@ -104,6 +108,9 @@ public:
     const rt_settings& render_settings() const { return s_; }
     int set_settings(const rt_settings& s);
     int set_exact(bool on);
+    // the octree of the next geometry changes is built on the device (rt_set_device_build)
+    void set_device_build(bool on) { knobs_.gpu_build = on; }
+    int64_t device_builds() const { return device_builds_; }
     // waits for the background build of the leaf cones / slabs and the wide BVH
     int finish_accel();
     bool exact() const { return knobs_.exact; }
@@ -251,6 +258,16 @@ private:
     uint64_t mir_accel_ = ~0ull;   // the lead's accel_ver_ copied
     int adopt_from_lead();
     int64_t host_builds_ = 0;      // host octree builds (rt_stats host_builds, helpers included)
+    // the device octree build (knobs_.gpu_build): its temporaries and totals, and the pinned buffer the
+    // triangles are staged through and the built arrays come back through
+    int64_t device_builds_ = 0;    // device octree builds (rt_get_device_builds)
+    std::unique_ptr<OctreeGpuScratch> oct_gpu_;
+    DevBuf d_oct_info_;
+    void* build_pin_ = nullptr;
+    size_t build_pin_bytes_ = 0;
+    // builds oct_ and d_nodes_ / d_tris_ / d_tri_id_ on the device; built stays false when the
+    // builder does not take the input (the caller builds on the host)
+    int build_octree_device(int64_t n, bool& built);
     struct MultiDev;
     std::unique_ptr<MultiDev> multi_;
     int num_cus_ = 256;

@@ -99,6 +99,17 @@ class Renderer:
         the reference does, instead of the certified wide BVH."""
         self._call("rt_set_exact", 1 if on else 0)
 
+    def set_device_build(self, on: bool = True):
+        """rt_set_device_build: the octree of the next geometry changes is built on the
+        GPU (the host build's bytes; inputs the device builder does not take build on the host)."""
+        self._call("rt_set_device_build", 1 if on else 0)
+
+    def device_builds(self) -> int:
+        """rt_get_device_builds: device octree builds since the renderer was created."""
+        n = C.c_int64()
+        self._call("rt_get_device_builds", C.byref(n))
+        return int(n.value)
+
     # -- geometry (renderer.h:57-62) ------------------------------------------------
     def set_triangles(self, tri9, mat, uv6=None):
         tri9 = f32(tri9).reshape(-1, 9)
