@@ -169,6 +169,32 @@ int rt_get_device_builds(rt_renderer *r, int64_t *count);
 int rt_octree_build_device(int32_t device, const float *tri9, int64_t n, int32_t max_depth, int32_t leaf_max_obj_count,
                            uint64_t *digest, int64_t stats[7], float ms[2]);
 
+/* The quick wide BVH on the device.  With the device build on, a rebuild whose
+ * octree was built on the device also builds the quick wide BVH there, from the device-resident octree
+ * into the tables the frames read: the same tree as the host's, byte for byte except the two codes
+ * that go through acos / cos / sin, which may differ by one step (both sound).  Otherwise the host
+ * builds it as before.  rt_get_device_wide_builds: such device builds since rt_create.
+ * RT_ACCEL_HOLD=1 at rt_create (tests): frames keep the quick tree until rt_finish_accel adopts the
+ * background's SAH tree. */
+int rt_get_device_wide_builds(rt_renderer *r, int64_t *count);
+
+/* The quick tree's builders alone.  rt_wbvh_quick_digest (host only): builds the octree and the quick
+ * tree of tri9 on the host and returns six 64-bit FNV-1a digests (rt_octree_digest's hash): 0 the
+ * nodes' exact fields (ox, oy, oz, exps, qlo, qhi, child), 1 s, slo, slab[] and bytes 0-2 of nrm[], 2
+ * ext bytes 0, 1, 3 and ext2, 3 the transcendental bytes (nrm byte 3, the cone code; ext byte 2, sth),
+ * 4 slot[] then leaf_of_slot[], 5 tri_leaf[] then parent[]; stats = nodes, leaves, tris, max_leaf,
+ * depth; ms (optional) the two builds' time.
+ * rt_wbvh_quick_build_device: the octree and the quick tree built on 'device' and downloaded: the
+ * same digests and stats; check[0] = the downloaded tree's structural violations against the octree,
+ * check[1] = transcendental bytes that differ from the host tree's, check[2] = the largest |code
+ * difference| among them, check[3] = differing bytes elsewhere; ms (optional) = {the device quick
+ * build by HIP events, the whole call}.  RT_EUNSUPPORTED / RT_EHIP as rt_octree_build_device. */
+int rt_wbvh_quick_digest(const float *tri9, int64_t n, int32_t max_depth, int32_t leaf_max_obj_count, uint64_t digest[6],
+                         int64_t stats[5], float *ms);
+int rt_wbvh_quick_build_device(int32_t device, const float *tri9, int64_t n, int32_t max_depth,
+                               int32_t leaf_max_obj_count, uint64_t digest[6], int64_t stats[5], int64_t check[4],
+                               float ms[2]);
+
 /* Single-process multi-device rendering (no reference counterpart: the reference renders on
  * one host, RenderThread::run, QT/mainWindowThreads.cpp:39-65).  ids[0] must be the handle's
  * device; n = 0 (or ids NULL) returns to one device.  rt_render then renders on every device

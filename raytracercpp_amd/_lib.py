@@ -142,6 +142,10 @@ SIGNATURES = {
                                          _i64p, _f32p]),
     "rt_set_device_build": (C.c_int, [_H, C.c_int]),
     "rt_get_device_builds": (C.c_int, [_H, _i64p]),
+    "rt_get_device_wide_builds": (C.c_int, [_H, _i64p]),
+    "rt_wbvh_quick_digest": (C.c_int, [_f32p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_uint64), _i64p, _f32p]),
+    "rt_wbvh_quick_build_device": (C.c_int, [C.c_int32, _f32p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_uint64),
+                                             _i64p, _i64p, _f32p]),
     "rt_debug_read": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_int64]),
     "rt_tile_costs": (C.c_int, [_H, C.POINTER(C.c_uint32), C.c_int64, _i32p, _i32p]),
     "rt_wbvh_query": (C.c_int, [_f32p, C.c_int64, C.c_int32, C.c_int32, _f32p, _f32p, C.c_int64, _i32p, _i32p, _f32p,
@@ -354,6 +358,40 @@ def octree_digest(tri9, max_depth=12, leaf=40, builder=0):
                                  ptr(st, _i64p), C.byref(ms)), "rt_octree_digest")
     keys = ("inner", "leaves", "empty_leaves", "max_leaf", "max_depth", "nodes", "levels")
     return int(dg.value), dict(zip(keys, map(int, st))), float(ms.value)
+
+
+_WQ_STATS = ("nodes", "leaves", "tris", "max_leaf", "depth")
+
+
+def wbvh_quick_digest(tri9, max_depth=12, leaf=40):
+    """rt_wbvh_quick_digest: (six digests, stats dict, build ms) of the quick wide BVH built on the host
+    (no GPU).  Digests: exact node fields, slabs, conditioning bytes, transcendental bytes (cone code,
+    sth), slot maps, links."""
+    tri9 = f32(tri9).reshape(-1, 9)
+    dg = (C.c_uint64 * 6)()
+    st = np.zeros(5, np.int64)
+    ms = C.c_float()
+    check(lib().rt_wbvh_quick_digest(ptr(tri9, _f32p), tri9.shape[0], max_depth, leaf, dg, ptr(st, _i64p),
+                                     C.byref(ms)), "rt_wbvh_quick_digest")
+    return tuple(int(x) for x in dg), dict(zip(_WQ_STATS, map(int, st))), float(ms.value)
+
+
+def wbvh_quick_build_device(tri9, max_depth=12, leaf=40, device=0):
+    """rt_wbvh_quick_build_device: (six digests, stats dict, check dict, (device quick build ms, whole call
+    ms)) of the quick wide BVH built on the GPU from the device-built octree.  check: violations
+    (check_wbvh of the downloaded tree), trans_diff / trans_max (transcendental bytes differing from the
+    host tree's, the largest code difference), other_diff (differing bytes elsewhere)."""
+    tri9 = f32(tri9).reshape(-1, 9)
+    dg = (C.c_uint64 * 6)()
+    st = np.zeros(5, np.int64)
+    ck = np.zeros(4, np.int64)
+    ms = np.zeros(2, np.float32)
+    check(lib().rt_wbvh_quick_build_device(device, ptr(tri9, _f32p), tri9.shape[0], max_depth, leaf, dg,
+                                           ptr(st, _i64p), ptr(ck, _i64p), ptr(ms, _f32p)),
+          "rt_wbvh_quick_build_device")
+    keys = ("violations", "trans_diff", "trans_max", "other_diff")
+    return (tuple(int(x) for x in dg), dict(zip(_WQ_STATS, map(int, st))), dict(zip(keys, map(int, ck))),
+            (float(ms[0]), float(ms[1])))
 
 
 def octree_build_device(tri9, max_depth=12, leaf=40, device=0):

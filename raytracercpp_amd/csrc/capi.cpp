@@ -13,6 +13,7 @@
 #include "octree_gpu.hpp"
 #include "ocone.hpp"
 #include "wbvh.hpp"
+#include "wbvh_quick_gpu.hpp"
 #include "renderer.hpp"
 
 namespace {
@@ -75,6 +76,99 @@ void octree_report(const rt::FlatOctree& f, uint64_t* digest, int64_t* stats)
         stats[5] = f.stats.nodes;
         stats[6] = f.levels;
     }
+}
+// rt_wbvh_quick_digest / rt_wbvh_quick_build_device: a quick tree's bytes by class (rt_mi355x.h): 0 the
+// nodes' exact fields, 1 the slabs, 2 the conditioning bytes, 3 the transcendental bytes (cone code,
+// sth), 4 the slot maps, 5 the links
+int wnode_byte_class(size_t off)
+{
+    if (off < 40)
+        return 0;                      // ox, oy, oz, exps, qlo, qhi
+    if (off < 48)
+        return 1;                      // s, slo
+    if (off < 64)
+        return (off & 3) == 3 ? 3 : 1; // nrm: the normal's bytes, the cone code
+    if (off < 80)
+        return 1;                      // slab
+    if (off < 96)
+        return 0;                      // child
+    if (off < 112)
+        return (off & 3) == 2 ? 3 : 2; // ext: smin, s2, sth, lmax
+    return 2;                          // ext2
+}
+
+void wquick_report(const rt::WBvh& w, uint64_t digest[6], int64_t stats[5])
+{
+    uint64_t h[6];
+    for (int k = 0; k < 6; k++) h[k] = 1469598103934665603ull;
+    auto mix = [&h](int k, const void* p, size_t len) {
+        const unsigned char* b = static_cast<const unsigned char*>(p);
+        for (size_t i = 0; i < len; i++) {
+            h[k] ^= b[i];
+            h[k] *= 1099511628211ull;
+        }
+    };
+    int cls[sizeof(rt::WNode)];
+    for (size_t o = 0; o < sizeof(rt::WNode); o++) cls[o] = wnode_byte_class(o);
+    for (const rt::WNode& n : w.nodes) {
+        const unsigned char* b = reinterpret_cast<const unsigned char*>(&n);
+        for (size_t o = 0; o < sizeof(rt::WNode); o++) mix(cls[o], b + o, 1);
+    }
+    mix(4, w.slot.data(), w.slot.size() * 4);
+    mix(4, w.leaf_of_slot.data(), w.leaf_of_slot.size() * 4);
+    mix(5, w.tri_leaf.data(), w.tri_leaf.size() * 4);
+    mix(5, w.parent.data(), w.parent.size() * 4);
+    for (int k = 0; k < 6; k++) digest[k] = h[k];
+    if (stats) {
+        stats[0] = w.stats.nodes;
+        stats[1] = w.stats.leaves;
+        stats[2] = w.stats.tris;
+        stats[3] = w.stats.max_leaf;
+        stats[4] = w.stats.depth;
+    }
+}
+
+// check[1..3] of rt_wbvh_quick_build_device: a (the device's tree) against b (the host's)
+void wquick_compare(const rt::WBvh& a, const rt::WBvh& b, int64_t check[4])
+{
+    int64_t trans = 0, maxd = 0, other = 0;
+    auto words = [&other](const auto& x, const auto& y) {
+        if (x.size() != y.size()) {
+            other += 4 * (int64_t)std::max(x.size(), y.size());
+            return;
+        }
+        const unsigned char* p = reinterpret_cast<const unsigned char*>(x.data());
+        const unsigned char* q = reinterpret_cast<const unsigned char*>(y.data());
+        for (size_t i = 0; i < x.size() * 4; i++) other += p[i] != q[i];
+    };
+    if (a.nodes.size() != b.nodes.size())
+        other += (int64_t)sizeof(rt::WNode) * (int64_t)std::max(a.nodes.size(), b.nodes.size());
+    else
+        for (size_t i = 0; i < a.nodes.size(); i++) {
+            const unsigned char* p = reinterpret_cast<const unsigned char*>(&a.nodes[i]);
+            const unsigned char* q = reinterpret_cast<const unsigned char*>(&b.nodes[i]);
+            for (size_t o = 0; o < sizeof(rt::WNode); o++) {
+                if (p[o] == q[o])
+                    continue;
+                if (wnode_byte_class(o) == 3) {
+                    trans++;
+                    maxd = std::max<int64_t>(maxd, std::abs((int)p[o] - (int)q[o]));
+                } else
+                    other++;
+            }
+        }
+    words(a.slot, b.slot);
+    words(a.leaf_of_slot, b.leaf_of_slot);
+    words(a.tri_leaf, b.tri_leaf);
+    words(a.parent, b.parent);
+    for (int k = 0; k < 5; k++) {
+        const int64_t sa[5] = {a.stats.nodes, a.stats.leaves, a.stats.tris, a.stats.max_leaf, a.stats.depth};
+        const int64_t sb[5] = {b.stats.nodes, b.stats.leaves, b.stats.tris, b.stats.max_leaf, b.stats.depth};
+        other += sa[k] != sb[k];
+    }
+    check[1] = trans;
+    check[2] = maxd;
+    check[3] = other;
 }
 }  // namespace
 
@@ -792,6 +886,155 @@ int rt_get_device_builds(rt_renderer* r, int64_t* count)
         *count = R(r)->device_builds();
         return RT_OK;
     });
+}
+
+int rt_get_device_wide_builds(rt_renderer* r, int64_t* count)
+{
+    return guarded(R(r), [&] {
+        if (!count)
+            return RT_EINVAL;
+        *count = R(r)->device_wide_builds();
+        return RT_OK;
+    });
+}
+
+int rt_wbvh_quick_digest(const float* tri9, int64_t n, int32_t max_depth, int32_t leaf_max_obj_count, uint64_t digest[6],
+                         int64_t stats[5], float* ms)
+{
+    if (n < 0 || (n > 0 && !tri9) || !digest)
+        return bad("rt_wbvh_quick_digest: bad arguments");
+    try {
+        rt::FlatOctree f;
+        rt::WBvh w;
+        auto t0 = std::chrono::steady_clock::now();
+        rt::build_flat_octree(tri9, n, max_depth, leaf_max_obj_count, f);
+        rt::build_wbvh_quick(f, w, false);
+        if (ms)
+            *ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        wquick_report(w, digest, stats);
+        return RT_OK;
+    } catch (const std::bad_alloc&) {
+        g_err = "rt_wbvh_quick_digest: out of host memory";
+        return RT_ENOMEM;
+    }
+}
+
+int rt_wbvh_quick_build_device(int32_t device, const float* tri9, int64_t n, int32_t max_depth,
+                               int32_t leaf_max_obj_count, uint64_t digest[6], int64_t stats[5], int64_t check[4],
+                               float ms[2])
+{
+    if (n < 0 || (n > 0 && !tri9) || !digest || !check)
+        return bad("rt_wbvh_quick_build_device: bad arguments");
+    auto t0 = std::chrono::steady_clock::now();
+    bool finite = true;
+    for (int64_t i = 0; i < 9 * n && finite; i++) finite = std::isfinite(tri9[i]);
+    if (!rt::wbvh_quick_device_supported(n, max_depth) || !finite) {
+        g_err = "rt_wbvh_quick_build_device: input outside the device builder's range";
+        return RT_EUNSUPPORTED;
+    }
+    auto hip_bad = [](hipError_t e, const char* what) {
+        g_err = std::string("rt_wbvh_quick_build_device: ") + what + ": " + hipGetErrorString(e);
+        return RT_EHIP;
+    };
+    try {
+        hipError_t e = hipSetDevice(device);
+        if (e != hipSuccess)
+            return hip_bad(e, "hipSetDevice");
+        rt::OctreeGpuScratch scratch;
+        rt::WQuickGpuScratch wscratch;
+        rt::DevBuf d_tri9, d_nodes, d_tris, d_tri_id, d_info, d_wnodes, d_wtmp, d_wlinks;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        struct EvGuard {
+            hipEvent_t* ev;
+            ~EvGuard()
+            {
+                for (int i = 0; i < 2; i++)
+                    if (ev[i]) (void)hipEventDestroy(ev[i]);
+            }
+        } guard{ev};
+        if ((e = d_tri9.reserve((size_t)n * 36)) != hipSuccess || (e = d_info.reserve(sizeof(rt::OctreeDevInfo))) != hipSuccess ||
+            (e = hipEventCreate(&ev[0])) != hipSuccess || (e = hipEventCreate(&ev[1])) != hipSuccess)
+            return hip_bad(e, "allocation");
+        if (n > 0 && (e = hipMemcpy(d_tri9.p, tri9, (size_t)n * 36, hipMemcpyHostToDevice)) != hipSuccess)
+            return hip_bad(e, "upload");
+        rt::OctreeDevInfo info;
+        int rc = rt::build_flat_octree_device(scratch, d_tri9.as<float>(), n, max_depth, leaf_max_obj_count, d_nodes,
+                                              d_tris, d_tri_id, d_info.as<rt::OctreeDevInfo>(), &info, nullptr, &e);
+        if (rc == rt::OCT_GPU_UNSUPPORTED) {
+            g_err = "rt_wbvh_quick_build_device: input outside the device builder's range";
+            return RT_EUNSUPPORTED;
+        }
+        if (rc != rt::OCT_GPU_OK)
+            return hip_bad(e, "octree build");
+        if ((e = hipEventRecord(ev[0], nullptr)) != hipSuccess)
+            return hip_bad(e, "hipEventRecord");
+        int64_t st[5];
+        rc = rt::build_wbvh_quick_device(wscratch, d_nodes.as<rt::GNode>(), d_tris.as<rt::GTri>(), info, d_wnodes, d_wtmp,
+                                         d_wlinks, st, nullptr, &e);
+        if (rc == rt::OCT_GPU_UNSUPPORTED) {
+            g_err = "rt_wbvh_quick_build_device: input outside the device builder's range";
+            return RT_EUNSUPPORTED;
+        }
+        if (rc != rt::OCT_GPU_OK)
+            return hip_bad(e, "quick wide BVH build");
+        float dev_ms = 0.0f;
+        if ((e = hipEventRecord(ev[1], nullptr)) != hipSuccess || (e = hipEventSynchronize(ev[1])) != hipSuccess ||
+            (e = hipEventElapsedTime(&dev_ms, ev[0], ev[1])) != hipSuccess)
+            return hip_bad(e, "timing");
+        rt::FlatOctree f;
+        f.nodes.resize((size_t)info.nodes);
+        f.tris.resize((size_t)info.tris);
+        f.tri_id.resize((size_t)info.tris);
+        f.levels = info.levels;
+        f.ordered_slabs = info.ordered_slabs != 0;
+        if (info.nodes &&
+            (e = hipMemcpy(f.nodes.data(), d_nodes.p, f.nodes.size() * sizeof(rt::GNode), hipMemcpyDeviceToHost)) != hipSuccess)
+            return hip_bad(e, "readback");
+        if (info.tris &&
+            ((e = hipMemcpy(f.tris.data(), d_tris.p, f.tris.size() * sizeof(rt::GTri), hipMemcpyDeviceToHost)) != hipSuccess ||
+             (e = hipMemcpy(f.tri_id.data(), d_tri_id.p, f.tri_id.size() * 4, hipMemcpyDeviceToHost)) != hipSuccess))
+            return hip_bad(e, "readback");
+        rt::WBvh w;
+        const size_t np = (size_t)st[0], nt = (size_t)st[2];
+        w.nodes.resize(np);
+        w.slot.resize(nt);
+        w.leaf_of_slot.resize(nt);
+        w.tri_leaf.resize(nt);
+        w.parent.resize(np);
+        if (np && ((e = hipMemcpy(w.nodes.data(), d_wnodes.p, np * sizeof(rt::WNode), hipMemcpyDeviceToHost)) != hipSuccess ||
+                   (e = hipMemcpy(w.slot.data(), d_wtmp.p, nt * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
+                   (e = hipMemcpy(w.leaf_of_slot.data(), d_wtmp.as<char>() + nt * 4, nt * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
+                   (e = hipMemcpy(w.tri_leaf.data(), d_wlinks.p, nt * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
+                   (e = hipMemcpy(w.parent.data(), d_wlinks.as<char>() + nt * 4, np * 4, hipMemcpyDeviceToHost)) != hipSuccess))
+            return hip_bad(e, "readback");
+        w.leaf_of_k.resize(nt);
+        for (size_t k = 0; k < nt; k++)
+            w.leaf_of_k[k] = (size_t)w.slot[k] < nt ? w.leaf_of_slot[(size_t)w.slot[k]] : 0u;
+        w.stats.nodes = st[0];
+        w.stats.leaves = st[1];
+        w.stats.tris = st[2];
+        w.stats.max_leaf = st[3];
+        w.stats.depth = st[4];
+        wquick_report(w, digest, stats);
+        rt::WBvh host;
+        rt::build_wbvh_quick(f, host, true);
+        wquick_compare(w, host, check);
+        bool slots_ok = true;
+        for (size_t k = 0; k < nt; k++) slots_ok = slots_ok && w.slot[k] >= 0 && (size_t)w.slot[k] < nt;
+        if (np && slots_ok) {
+            rt::wbvh_fill_tris(f, w);
+            check[0] = rt::check_wbvh(f, w);
+        } else
+            check[0] = np ? 1 : 0;
+        if (ms) {
+            ms[0] = dev_ms;
+            ms[1] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+        return RT_OK;
+    } catch (const std::bad_alloc&) {
+        g_err = "rt_wbvh_quick_build_device: out of host memory";
+        return RT_ENOMEM;
+    }
 }
 
 #if defined(W_DIAG) && !defined(__HIP_DEVICE_COMPILE__)

@@ -15,6 +15,7 @@
 #include "host_scene.hpp"
 #include "launch.hpp"
 #include "octree_gpu.hpp"
+#include "wbvh_quick_gpu.hpp"
 
 namespace rt {
 
@@ -103,6 +104,7 @@ Knobs Knobs::from_env()
     k.inject_fail = num("RT_INJECT_FRAME_FAIL", 0);   // tests: the k-th ray_trace fails after its image start
     k.async_accel = on("RT_ASYNC_ACCEL", true);
     k.gpu_build = flag("RT_GPU_BUILD", k.gpu_build);
+    k.accel_hold = flag("RT_ACCEL_HOLD", k.accel_hold);
     const int chunk = num("RT_REFL_CHUNK_LOG2", k.refl_chunk_log2);
     if (chunk >= 10 && chunk <= 27)   // small values (tests): many chunks per level
         k.refl_chunk_log2 = chunk;
@@ -335,8 +337,8 @@ int Renderer::set_light_position(float x, float y, float z)
 // reference's own traversal; leaving it rebuilds the wide BVH if it was never built.
 int Renderer::set_exact(bool on)
 {
-    poll_accel(true);   // (reads wb_)
-    if (knobs_.exact && !on && knobs_.wbvh && wb_.nodes.empty() && s_.enable_bvh)
+    poll_accel(true, true);   // (reads wb_)
+    if (knobs_.exact && !on && knobs_.wbvh && wb_.nodes.empty() && !wb_on_device_ && s_.enable_bvh)
         geom_dirty_ = true, ++geom_ver_;
     knobs_.exact = on;
     return RT_OK;
@@ -705,10 +707,12 @@ void Renderer::start_accel()
 
 // Adopts a finished background build (wait: blocks until it is, the origin cones included): the SAH
 // tree as soon as it is resident, the origin cones when the thread is done.
-int Renderer::poll_accel(bool wait)
+int Renderer::poll_accel(bool wait, bool release)
 {
     if (!accel_thread_.joinable())
         return RT_OK;
+    if (knobs_.accel_hold && !release)
+        return RT_OK;   // (RT_ACCEL_HOLD: the resident tree stays until rt_finish_accel)
     if (!wait && accel_state_.load() == 1)
         return RT_OK;
     if (wait || accel_state_.load() == 3 || oc_done_.load()) {
@@ -734,19 +738,23 @@ int Renderer::poll_accel(bool wait)
             // keep reading the old buffers, which the next geometry change rewrites only after waiting for them
             std::swap(wb_, wb_next_);
             wb_next_ = WBvh();
+            wb_on_device_ = false;
             d_wnodes_.swap(d_wnodes2_);
             d_wtris_.swap(d_wtris2_);
             d_wmeta_.swap(d_wmeta2_);
             d_wtmp_.swap(d_wtmp2_);
             d_wlinks_.swap(d_wlinks2_);
         }
-        wide_ready_ = !wb_.nodes.empty();
+        // (a device-built quick tree that stays resident keeps its counts: wb_ is not its host copy)
+        const int64_t wn = wb_on_device_ ? risk_nodes_ : (int64_t)wb_.nodes.size();
+        const int64_t wt = wb_on_device_ ? risk_tris_ : (int64_t)wb_.tri_leaf.size();
+        wide_ready_ = wn > 0;
         wide_tree_ = wide_ready_ ? 2 : 0;
-        if (wide_ready_ && reserve_risk(wb_.nodes.size()) != RT_OK)
+        if (wide_ready_ && reserve_risk((size_t)wn) != RT_OK)
             return RT_EHIP;
         risk_valid_ = false;
-        risk_nodes_ = (int64_t)wb_.nodes.size();
-        risk_tris_ = (int64_t)wb_.tri_leaf.size();
+        risk_nodes_ = wn;
+        risk_tris_ = wt;
         ++accel_ver_;
         build_split_ms_[1] = accel_ms_[0];
         build_split_ms_[2] = accel_ms_[1] + accel_ms_[2];
@@ -767,7 +775,7 @@ int Renderer::finish_accel()
     hipError_t e = hipSetDevice(device_);
     if (e != hipSuccess)
         return hip_fail(e, "hipSetDevice");
-    return poll_accel(true);
+    return poll_accel(true, true);
 }
 
 // A multi-device helper's scene (rt_set_devices): the lead has built and uploaded the octree
@@ -786,7 +794,7 @@ int Renderer::adopt_from_lead()
             e = hipMemcpyPeerAsync(dst.p, device_, src.p, L.device_, n, stream_);
     };
     if (geom_dirty_) {
-        poll_accel(true);
+        poll_accel(true, true);
         cones_ready_ = wide_ready_ = lslab_ready_ = ocone_ready_ = false;
         auto t0 = std::chrono::steady_clock::now();
         oct_ = FlatOctree();   // (never built here)
@@ -822,12 +830,14 @@ int Renderer::adopt_from_lead()
             }
         }
         if (L.wide_ready_) {
-            copy(d_wnodes_, L.d_wnodes_, L.wb_.nodes.size() * sizeof(WNode));
-            copy(d_wtris_, L.d_wtris_, L.wb_.slot.size() * sizeof(GTri));
-            copy(d_wmeta_, L.d_wmeta_, L.wb_.slot.size() * 16);
-            copy(d_wlinks_, L.d_wlinks_, (L.wb_.tri_leaf.size() + L.wb_.parent.size()) * 4);
+            // (the lead's counts: its tree may be device-built, with no host copy)
+            const size_t wn = (size_t)L.risk_nodes_, wt = (size_t)L.risk_tris_;
+            copy(d_wnodes_, L.d_wnodes_, wn * sizeof(WNode));
+            copy(d_wtris_, L.d_wtris_, wt * sizeof(GTri));
+            copy(d_wmeta_, L.d_wmeta_, wt * 16);
+            copy(d_wlinks_, L.d_wlinks_, (wt + wn) * 4);
             if (e == hipSuccess)
-                e = d_wrisk_.reserve(L.wb_.nodes.size() * 288 + 64);
+                e = d_wrisk_.reserve(wn * 288 + 64);
         }
         if (e == hipSuccess)
             e = hipStreamSynchronize(stream_);
@@ -905,7 +915,9 @@ int Renderer::build_octree_device(int64_t n, bool& built)
         (void)hipStreamSynchronize(stream_);
         return hip_fail(e, "upload (device octree build)");
     }
-    OctreeDevInfo info;
+    if (!oct_dev_info_)
+        oct_dev_info_ = std::make_unique<OctreeDevInfo>();
+    OctreeDevInfo& info = *oct_dev_info_;
     int rc = build_flat_octree_device(*oct_gpu_, d_tri9_.as<float>(), n, s_.bvh_max_depth, s_.bvh_leaf_object_count,
                                       d_nodes_, d_tris_, d_tri_id_, d_oct_info_.as<OctreeDevInfo>(), &info, stream_,
                                       &e);
@@ -963,6 +975,79 @@ int Renderer::build_octree_device(int64_t n, bool& built)
     return RT_OK;
 }
 
+// The quick wide BVH by the device builder, from the octree build_octree_device left in d_nodes_ /
+// d_tris_: the nodes, the slot maps (d_wtmp_) and the links in place, then the records' gather.  built
+// stays false when the builder does not take the input or a HIP call fails before the tables are used
+// (the caller then builds on the host from the read-back octree: the same tree).
+int Renderer::build_wide_device(bool& built)
+{
+    built = false;
+    const int64_t n = (int64_t)tri_mat_.size();
+    if (!oct_dev_info_ || !wbvh_quick_device_supported(n, s_.bvh_max_depth))
+        return RT_OK;
+    if (!wq_gpu_)
+        wq_gpu_ = std::make_unique<WQuickGpuScratch>();
+    hipError_t e = hipSuccess;
+    int64_t st[5] = {};
+    int rc = build_wbvh_quick_device(*wq_gpu_, d_nodes_.as<GNode>(), d_tris_.as<GTri>(), *oct_dev_info_, d_wnodes_,
+                                     d_wtmp_, d_wlinks_, st, stream_, &e);
+    if (rc == OCT_GPU_OK && st[0] > 0) {
+        const size_t nk = (size_t)st[2];
+        if ((e = d_wtris_.reserve(nk * sizeof(GTri))) == hipSuccess && (e = d_wmeta_.reserve(nk * 16)) == hipSuccess)
+            e = rt_launch_wide_gather(d_tris_.as<GTri>(), d_wtmp_.as<int32_t>(), d_wtmp_.as<uint32_t>() + nk,
+                                      d_tri_id_.as<int32_t>(), d_tri_mat_.as<int32_t>(), (int)nk, d_wtris_.as<GTri>(),
+                                      d_wmeta_.as<uint4>(), stream_);
+        if (e != hipSuccess)
+            rc = OCT_GPU_HIP;
+    }
+    if (rc == OCT_GPU_HIP) {
+        // (a sticky error fails the host path's upload just after; any other is left behind)
+        (void)hipGetLastError();
+        return RT_OK;
+    }
+    if (rc != OCT_GPU_OK || st[0] <= 0)
+        return RT_OK;
+    wb_dev_stats_ = WStats();
+    wb_dev_stats_.nodes = st[0];
+    wb_dev_stats_.leaves = st[1];
+    wb_dev_stats_.tris = st[2];
+    wb_dev_stats_.max_leaf = st[3];
+    wb_dev_stats_.depth = st[4];
+    ++device_wide_builds_;
+    built = true;
+    return RT_OK;
+}
+
+// The host copy of a device-built quick tree, for the host readers of wb_ (rt_risk_words): one download
+int Renderer::host_wide()
+{
+    if (!wb_on_device_ || !wb_.nodes.empty())
+        return RT_OK;
+    hipError_t e = hipSetDevice(device_);
+    const size_t np = (size_t)risk_nodes_, nt = (size_t)risk_tris_;
+    WBvh w;
+    w.nodes.resize(np);
+    w.slot.resize(nt);
+    w.leaf_of_slot.resize(nt);
+    w.tri_leaf.resize(nt);
+    w.parent.resize(np);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(stream_);
+    if (e == hipSuccess) e = hipMemcpy(w.nodes.data(), d_wnodes_.p, np * sizeof(WNode), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(w.slot.data(), d_wtmp_.p, nt * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(w.leaf_of_slot.data(), d_wtmp_.as<char>() + nt * 4, nt * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(w.tri_leaf.data(), d_wlinks_.p, nt * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(w.parent.data(), d_wlinks_.as<char>() + nt * 4, np * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess)
+        return hip_fail(e, "download (device-built quick wide BVH)");
+    w.leaf_of_k.resize(nt);
+    for (size_t k = 0; k < nt; k++)
+        w.leaf_of_k[k] = w.leaf_of_slot[(size_t)w.slot[k]];
+    w.stats = wb_dev_stats_;
+    wb_ = std::move(w);
+    return RT_OK;
+}
+
 int Renderer::ensure_device_scene()
 {
     hipError_t e = hipSetDevice(device_);
@@ -977,7 +1062,7 @@ int Renderer::ensure_device_scene()
             return rc;
     } else if (geom_dirty_) {
         // a build of the previous geometry reads oct_: let it finish (its result is dropped)
-        poll_accel(true);
+        poll_accel(true, true);
         cones_ready_ = wide_ready_ = lslab_ready_ = ocone_ready_ = false;
         using clk = std::chrono::steady_clock;
         auto ms_since = [](clk::time_point t) { return std::chrono::duration<float, std::milli>(clk::now() - t).count(); };
@@ -1048,7 +1133,13 @@ int Renderer::ensure_device_scene()
         const bool quick = e == hipSuccess && s_.enable_bvh && knobs_.quick_wbvh && knobs_.wbvh && !knobs_.exact &&
                            oct_nn_ > 0;
         wb_ = WBvh();
-        if (quick) {   // (its time counts in build_ms, the blocking part; build_split_ms[2] is the SAH tree's)
+        wb_on_device_ = false;
+        if (quick && dev_built) {   // (the octree is in HBM: the quick tree is built from it where it lies)
+            int rc = build_wide_device(wb_on_device_);
+            if (rc != RT_OK)
+                return rc;
+        }
+        if (quick && !wb_on_device_) {   // (its time counts in build_ms, the blocking part; build_split_ms[2] is the SAH tree's)
             build_wbvh_quick(oct_, wb_, false);   // (records gathered on the device)
             if (!wb_.nodes.empty())
                 e = upload_wide(wb_, d_wnodes_, d_wtris_, d_wmeta_, d_wtmp_, d_wlinks_, stream_);
@@ -1063,15 +1154,17 @@ int Renderer::ensure_device_scene()
         build_ms_ = ms_since(t0);
         build_split_ms_[1] = 0.0f;
         wide_tree_ = 0;
-        if (!wb_.nodes.empty()) {
+        const int64_t wn = wb_on_device_ ? wb_dev_stats_.nodes : (int64_t)wb_.nodes.size();
+        const int64_t wt = wb_on_device_ ? wb_dev_stats_.tris : (int64_t)wb_.tri_leaf.size();
+        if (wn > 0) {
             wide_ready_ = true;
             wide_tree_ = 1;
-            int rc = reserve_risk(wb_.nodes.size());
+            int rc = reserve_risk((size_t)wn);
             if (rc != RT_OK)
                 return rc;
             risk_valid_ = false;
-            risk_nodes_ = (int64_t)wb_.nodes.size();
-            risk_tris_ = (int64_t)wb_.tri_leaf.size();
+            risk_nodes_ = wn;
+            risk_tris_ = wt;
             ++accel_ver_;
         }
         build_split_ms_[2] = 0.0f;
@@ -1088,6 +1181,7 @@ int Renderer::ensure_device_scene()
             lslab_.clear();
             lsin_.clear();
             wb_ = WBvh();
+            wb_on_device_ = false;
         }
     } else {
         int rc = poll_accel(false);
@@ -2518,6 +2612,8 @@ int Renderer::risk_words(int src, uint64_t* out, int64_t cap, int64_t* count, in
             (e = hipStreamSynchronize(stream_)) != hipSuccess)
             return hip_fail(e, "download (risk words)");
     }
+    if ((rc = host_wide()) != RT_OK)
+        return rc;
     if (wb_.tris.size() != wb_.slot.size())
         wbvh_fill_tris(oct_, wb_);   // (the quick tree keeps no host copy of the records)
     const float lo[3] = {oct_root_.dn[0], oct_root_.dn[1], oct_root_.dn[2]};

@@ -23,6 +23,8 @@
 namespace rt {
 
 struct OctreeGpuScratch;   // octree_gpu.hpp
+struct OctreeDevInfo;
+struct WQuickGpuScratch;   // wbvh_quick_gpu.hpp
 
 struct DevBuf {
     void* p = nullptr;
@@ -95,6 +97,8 @@ struct Knobs {
                               // (octree_gpu.hpp; the same bytes as the host build)
     bool async_accel = true;  // RT_ASYNC_ACCEL=0: the leaf cones / slabs and the wide BVH are built
                               // before the first frame instead of beside it
+    bool accel_hold = false;  // RT_ACCEL_HOLD=1 (tests): frames keep the quick wide BVH until rt_finish_accel
+                              // adopts the background's SAH tree
     static Knobs from_env();
 };
 
@@ -111,6 +115,7 @@ public:
     // the octree of the next geometry changes is built on the device (rt_set_device_build)
     void set_device_build(bool on) { knobs_.gpu_build = on; }
     int64_t device_builds() const { return device_builds_; }
+    int64_t device_wide_builds() const { return device_wide_builds_; }
     // waits for the background build of the leaf cones / slabs and the wide BVH
     int finish_accel();
     bool exact() const { return knobs_.exact; }
@@ -250,7 +255,8 @@ private:
     int wide_tree_ = 0;   // rt_stats.wide_tree: 0 none, 1 the quick tree, 2 the SAH tree, -1 its build failed
     uint64_t accel_ver_ = 0;   // bumped when poll_accel adopts a build
     void start_accel();
-    int poll_accel(bool wait);
+    // release: adopt even under RT_ACCEL_HOLD (rt_finish_accel, and before the geometry is replaced)
+    int poll_accel(bool wait, bool release = false);
     void mirror_from(const Renderer& lead);
     // a multi-device helper (rt_set_devices): the lead builds the octree, the leaf cones / slabs
     // and the wide BVH once; a helper copies the lead's device buffers to its own device
@@ -268,6 +274,16 @@ private:
     // builds oct_ and d_nodes_ / d_tris_ / d_tri_id_ on the device; built stays false when the
     // builder does not take the input (the caller builds on the host)
     int build_octree_device(int64_t n, bool& built);
+    // the quick wide BVH of a device-built octree, built there too (wbvh_quick_gpu.hpp):
+    // d_wnodes_ / d_wtris_ / d_wmeta_ / d_wlinks_ written in place.  wb_ then stays empty (wb_on_device_)
+    // until a host reader asks for it (host_wide: one download); the counts are risk_nodes_ / risk_tris_.
+    int64_t device_wide_builds_ = 0;
+    std::unique_ptr<OctreeDevInfo> oct_dev_info_;   // the last device octree build's totals
+    std::unique_ptr<WQuickGpuScratch> wq_gpu_;
+    bool wb_on_device_ = false;
+    WStats wb_dev_stats_;
+    int build_wide_device(bool& built);
+    int host_wide();
     struct MultiDev;
     std::unique_ptr<MultiDev> multi_;
     int num_cus_ = 256;

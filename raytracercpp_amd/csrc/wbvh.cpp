@@ -2,6 +2,7 @@
 // records: binned SAH binary tree (16 bins per axis, parallel over subtrees), collapsed
 // to 4-wide nodes by repeatedly opening the child with the largest surface area.
 #include "wbvh.hpp"
+#include "wbvh_quick.hpp"
 #include "pool.hpp"
 
 #include <algorithm>
@@ -18,50 +19,16 @@
 
 namespace rt {
 
+using namespace quick;   // the boxes and the quick tree's per-node arithmetic (wbvh_quick.hpp)
+
 namespace {
 
-struct Box {
-    float lo[3], hi[3];
-};
-
-inline Box empty_box() { return Box{{INFINITY, INFINITY, INFINITY}, {-INFINITY, -INFINITY, -INFINITY}}; }
-inline void grow(Box& b, const Box& o)
-{
-    for (int a = 0; a < 3; a++) {
-        b.lo[a] = std::min(b.lo[a], o.lo[a]);
-        b.hi[a] = std::max(b.hi[a], o.hi[a]);
-    }
-}
 inline float area(const Box& b)
 {
     float dx = b.hi[0] - b.lo[0], dy = b.hi[1] - b.lo[1], dz = b.hi[2] - b.lo[2];
     if (!(dx >= 0 && dy >= 0 && dz >= 0))
         return 0.0f;
     return 2.0f * (dx * dy + dy * dz + dz * dx);
-}
-
-// float lower / upper bound of a double
-inline float down(double x)
-{
-    float f = (float)x;
-    return (double)f > x ? std::nextafter(f, -INFINITY) : f;
-}
-inline float up(double x)
-{
-    float f = (float)x;
-    return (double)f < x ? std::nextafter(f, INFINITY) : f;
-}
-
-// the box of a record's vertices a, a + ab, a + ac (exact sums in double, rounded outward)
-Box tri_box(const GTri& g)
-{
-    Box b;
-    for (int c = 0; c < 3; c++) {
-        double a = g.a[c], p = a + (double)g.ab[c], q = a + (double)g.ac[c];
-        b.lo[c] = down(std::min(a, std::min(p, q)));
-        b.hi[c] = up(std::max(a, std::max(p, q)));
-    }
-    return b;
 }
 
 struct BNode {
@@ -515,43 +482,6 @@ struct Builder {
     }
 };
 
-// The conditioning bytes (wbvh.hpp wq_val): the largest code whose value is <= x (a lower
-// bound on a sine in [0, 1]), and the smallest code whose value is >= x (an upper bound; for
-// lengths 255 = no bound).
-uint32_t wq_code_lb(double x)
-{
-    if (!(x > 0))
-        return 0u;
-    if (x >= 1)
-        return 255u;
-    float f = (float)x;
-    if ((double)f > x)
-        f = std::nextafter(f, 0.0f);
-    uint32_t bits;
-    std::memcpy(&bits, &f, 4);
-    if (bits < WQ_UNIT + (1u << 20))
-        return 0u;
-    const uint32_t k = (bits - WQ_UNIT) >> 20;
-    return k > 255u ? 255u : k;
-}
-
-uint32_t wq_code_ub(double x, uint32_t base)
-{
-    if (!(x > 0))
-        return x == 0 ? 0u : 255u;   // (NaN: no bound)
-    float f = (float)x;
-    if ((double)f < x)
-        f = std::nextafter(f, INFINITY);
-    uint32_t bits;
-    std::memcpy(&bits, &f, 4);
-    if (bits <= base + (1u << 20))
-        return 1u;
-    const uint32_t k = (bits - base + (1u << 20) - 1u) >> 20;
-    if (base == WQ_UNIT)
-        return k > 255u ? 255u : k;
-    return k > 254u ? 255u : k;
-}
-
 // One 4-wide node: the children's float boxes quantised to 8 bits per plane against the
 // node box's low corner, low planes rounded down and high planes up (exact in double:
 // origin, q and the power-of-two step are all representable), so each decoded box holds
@@ -695,21 +625,6 @@ WNode quantise(const Box* cb, const uint32_t* link, int nc, const ChildGeom* cg,
         w.slab[j] = (uint32_t)q0 | ((uint32_t)q1 << 16);
     }
     return w;
-}
-
-// the decoded box of child j (double, exact)
-Box decode(const WNode& w, int j, double lo[3], double hi[3])
-{
-    const float org[3] = {w.ox, w.oy, w.oz};
-    Box b;
-    for (int a = 0; a < 3; a++) {
-        const double st = std::ldexp(1.0, (int)((w.exps >> (8 * a)) & 0xffu) - 127);
-        lo[a] = org[a] + w.qlo[a][j] * st;
-        hi[a] = org[a] + w.qhi[a][j] * st;
-        b.lo[a] = down(lo[a]);
-        b.hi[a] = up(hi[a]);
-    }
-    return b;
 }
 
 // The 4-wide topology: each wide node opens the binary child with the largest surface area
@@ -1157,223 +1072,6 @@ void build_wbvh(const FlatOctree& oct, WBvh& out)
 // angle(N_c, N)), min / max for the rest.  Its float box holds its octree node's axis box, so rho = 0
 // above the octree leaves (as in the two-level SAH tree).  check_wbvh verifies all of it like the SAH
 // tree's.
-namespace {
-
-struct QChild {
-    Box box;
-    uint32_t link = W_EMPTY;   // W_LEAF | first << 3 | (count - 1), or a node index
-    double ns[3] = {0, 0, 0};  // sum of the stored normals (the slab normal's direction)
-    int nq[3] = {1, 0, 0};     // the quantised slab normal (quantise's rule)
-    double slo = INFINITY, shi = -INFINITY;   // range of nq . v over the triangles' vertices (absolute)
-    double tc = 0, ts = 0;     // half-angles between nq and the stored normals / the exact normals below
-    bool nocone = false, nosth = false;
-    double smin = 1.0, s2 = 1.0, lmax = 0.0;
-    int32_t leaf = -1;         // a run of an octree leaf's triangles: that leaf (rho against its axis box)
-};
-
-inline void q_normal(QChild& c)
-{
-    const double len = std::sqrt(c.ns[0] * c.ns[0] + c.ns[1] * c.ns[1] + c.ns[2] * c.ns[2]);
-    for (int a = 0; a < 3; a++)
-        c.nq[a] = len > 0 ? (int)std::lround(127.0 * c.ns[a] / len) : (a == 0 ? 1 : 0);
-    if (c.nq[0] == 0 && c.nq[1] == 0 && c.nq[2] == 0)
-        c.nq[0] = 1;
-}
-
-inline double q_len(const int* q) { return std::sqrt((double)q[0] * q[0] + (double)q[1] * q[1] + (double)q[2] * q[2]); }
-
-// angle between two quantised normals, rounded up (acos near 1 turns the cosine's rounding, ~1e-16,
-// into ~1.5e-8 of angle: 1e-7 of slack)
-inline double q_angle(const int* a, const int* b)
-{
-    const double c = ((double)a[0] * b[0] + (double)a[1] * b[1] + (double)a[2] * b[2]) / (q_len(a) * q_len(b));
-    return std::acos(std::max(-1.0, std::min(1.0, c))) + 1e-7;
-}
-
-// a run of triangles [first, first + cnt) of the wide order (record i: t[map[i]]): everything from the
-// triangles themselves
-void q_from_tris(QChild& c, const GTri* t, const int32_t* map, int32_t first, int32_t cnt)
-{
-    c.box = empty_box();
-    for (int a = 0; a < 3; a++)
-        c.ns[a] = 0;
-    for (int32_t i = first; i < first + cnt; i++) {
-        const GTri& T = t[map[i]];
-        grow(c.box, tri_box(T));
-        for (int a = 0; a < 3; a++)
-            c.ns[a] += (double)T.n[a];
-    }
-    q_normal(c);
-    const double n0 = c.nq[0], n1 = c.nq[1], n2 = c.nq[2], NL = q_len(c.nq);
-    double cmin = 1.0, smn = 1.0;   // stored normals (cone), exact normals (sth)
-    for (int32_t i = first; i < first + cnt; i++) {
-        const GTri& T = t[map[i]];
-        const double a0 = T.a[0], a1 = T.a[1], a2 = T.a[2];
-        const double s0 = n0 * a0 + n1 * a1 + n2 * a2;
-        const double s1 = n0 * (a0 + (double)T.ab[0]) + n1 * (a1 + (double)T.ab[1]) + n2 * (a2 + (double)T.ab[2]);
-        const double sv = n0 * (a0 + (double)T.ac[0]) + n1 * (a1 + (double)T.ac[1]) + n2 * (a2 + (double)T.ac[2]);
-        c.slo = std::min(c.slo, std::min(s0, std::min(s1, sv)));
-        c.shi = std::max(c.shi, std::max(s0, std::max(s1, sv)));
-        const double m0 = T.n[0], m1 = T.n[1], m2 = T.n[2];
-        const double mlen = std::sqrt(m0 * m0 + m1 * m1 + m2 * m2);
-        if (mlen == 0)
-            continue;   // Mdet = 0: never a hit (no cone, no conditioning bound needed)
-        if (!(mlen > 1e-30 && mlen < 1e27))
-            c.nocone = true;
-        else
-            cmin = std::min(cmin, (m0 * n0 + m1 * n1 + m2 * n2) / (mlen * NL));
-        const double x0 = T.ab[0], x1 = T.ab[1], x2 = T.ab[2], y0 = T.ac[0], y1 = T.ac[1], y2 = T.ac[2];
-        const double c0 = x1 * y2 - x2 * y1, c1 = x2 * y0 - x0 * y2, c2 = x0 * y1 - x1 * y0;
-        const double la = std::sqrt(x0 * x0 + x1 * x1 + x2 * x2), lc = std::sqrt(y0 * y0 + y1 * y1 + y2 * y2);
-        const double cl = std::sqrt(c0 * c0 + c1 * c1 + c2 * c2);
-        c.lmax = std::max(c.lmax, std::max(la, lc) * (1 + 1e-12));
-        c.smin = std::min(c.smin, sin_at_a_lb(T));
-        if (!(la * lc > 0x1p-100) || !(cl > 0x1p-50 * la * lc)) {
-            c.s2 = 0.0;
-            c.nosth = true;
-            continue;
-        }
-        const double ca = std::fabs(x0 * y0 + x1 * y1 + x2 * y2) / (la * lc);
-        c.s2 = std::min(c.s2, std::sqrt(std::max(0.0, (1.0 - std::min(1.0, ca + 1e-12)) / 2.0)) * (1 - 1e-9));
-        smn = std::min(smn, (c0 * n0 + c1 * n1 + c2 * n2) / (cl * NL) - 1e-12);
-    }
-    c.tc = std::acos(std::max(-1.0, std::min(1.0, cmin))) + 1e-7;
-    c.ts = std::acos(std::max(-1.0, std::min(1.0, smn))) + 1e-7;
-}
-
-// an upper child from its children (and the octree node's axis box, which it holds)
-void q_combine(QChild& p, const QChild* ch, int nc, const Box* extra)
-{
-    p.box = empty_box();
-    if (extra)
-        p.box = *extra;
-    for (int a = 0; a < 3; a++)
-        p.ns[a] = 0;
-    p.nocone = p.nosth = false;
-    p.smin = p.s2 = 1.0;
-    p.lmax = 0.0;
-    for (int i = 0; i < nc; i++) {
-        grow(p.box, ch[i].box);
-        for (int a = 0; a < 3; a++)
-            p.ns[a] += ch[i].ns[a];
-        p.nocone |= ch[i].nocone;
-        p.nosth |= ch[i].nosth;
-        p.smin = std::min(p.smin, ch[i].smin);
-        p.s2 = std::min(p.s2, ch[i].s2);
-        p.lmax = std::max(p.lmax, ch[i].lmax);
-    }
-    q_normal(p);
-    p.tc = p.ts = 0;
-    for (int i = 0; i < nc; i++) {
-        const double d = q_angle(p.nq, ch[i].nq);
-        p.tc = std::max(p.tc, d + ch[i].tc);
-        p.ts = std::max(p.ts, d + ch[i].ts);
-    }
-    // the slab: the range of nq . v over the box's corners (the box holds every vertex below)
-    p.slo = INFINITY;
-    p.shi = -INFINITY;
-    for (int k = 0; k < 8; k++) {
-        const double v0 = (k & 1) ? p.box.hi[0] : p.box.lo[0], v1 = (k & 2) ? p.box.hi[1] : p.box.lo[1],
-                     v2 = (k & 4) ? p.box.hi[2] : p.box.lo[2];
-        const double sv = p.nq[0] * v0 + p.nq[1] * v1 + p.nq[2] * v2;
-        p.slo = std::min(p.slo, sv);
-        p.shi = std::max(p.shi, sv);
-    }
-    p.leaf = -1;
-}
-
-// the node's boxes (quantise's rule), then per child the slab (absolute range shifted to the node's
-// origin, widened by the rounding of that shift), the cone code, the conditioning bytes and rho
-WNode q_node(const QChild* ch, int nc, const FlatOctree& oct)
-{
-    WNode w;
-    std::memset(&w, 0, sizeof(w));
-    Box nb = empty_box();
-    for (int j = 0; j < nc; j++)
-        grow(nb, ch[j].box);
-    const float org[3] = {nb.lo[0], nb.lo[1], nb.lo[2]};
-    w.ox = org[0];
-    w.oy = org[1];
-    w.oz = org[2];
-    for (int a = 0; a < 3; a++) {
-        const double ext = (double)nb.hi[a] - (double)org[a];
-        int k = -100;
-        if (ext > 0) {
-            int e;
-            std::frexp(ext / 255.0, &e);
-            k = std::max(-100, std::min(127, e - 1));
-            while (k < 127 && std::ldexp(255.0, k) < ext)
-                k++;
-        }
-        w.exps |= (uint32_t)(127 + k) << (8 * a);
-        const double st = std::ldexp(1.0, k);
-        for (int j = 0; j < nc; j++) {
-            const double lo = std::floor(((double)ch[j].box.lo[a] - org[a]) / st);
-            const double hi = std::ceil(((double)ch[j].box.hi[a] - org[a]) / st);
-            w.qlo[a][j] = (uint8_t)std::max(0.0, std::min(255.0, lo));
-            w.qhi[a][j] = (uint8_t)std::max(0.0, std::min(255.0, hi));
-        }
-    }
-    for (int j = 0; j < W_WIDTH; j++)
-        w.child[j] = j < nc ? ch[j].link : W_EMPTY;
-    double lo[W_WIDTH], hi[W_WIDTH], lo_all = INFINITY, hi_all = -INFINITY;
-    for (int j = 0; j < nc; j++) {
-        const double sh = (double)ch[j].nq[0] * org[0] + (double)ch[j].nq[1] * org[1] + (double)ch[j].nq[2] * org[2];
-        // |rounding| of the absolute sums and of the shift: a few ulps of the largest magnitude
-        const double slack = 0x1p-48 * (std::fabs(ch[j].slo) + std::fabs(ch[j].shi) + std::fabs(sh) +
-                                        128.0 * (std::fabs((double)org[0]) + std::fabs((double)org[1]) + std::fabs((double)org[2])));
-        lo[j] = ch[j].slo - sh - slack;
-        hi[j] = ch[j].shi - sh + slack;
-        lo_all = std::min(lo_all, lo[j]);
-        hi_all = std::max(hi_all, hi[j]);
-    }
-    const float slo = down(lo_all);
-    const double ext = hi_all - (double)slo;
-    int k = -100;
-    if (ext > 0) {
-        int e;
-        std::frexp(ext / 65535.0, &e);
-        k = std::max(-100, std::min(127, e - 1));
-        while (k < 127 && std::ldexp(65535.0, k) < ext)
-            k++;
-    }
-    const double st = std::ldexp(1.0, k);
-    w.s = (float)st;
-    w.slo = slo;
-    for (int j = 0; j < nc; j++) {
-        const QChild& c = ch[j];
-        // the cone code (cone_code's rule) from the half-angle
-        int code = 255;
-        const double NL = q_len(c.nq);
-        const double psi = std::acos(W_CONE_EPS) - c.tc - 1e-9;
-        if (!c.nocone && psi > 0) {
-            const double cd = std::ceil((std::cos(psi) * NL + 0.01) / ((double)W_CONE_STEP * (1 - 1e-9)));
-            code = cd <= 254 ? (int)cd : 255;
-        }
-        w.nrm[j] = (uint32_t)(uint8_t)(int8_t)c.nq[0] | ((uint32_t)(uint8_t)(int8_t)c.nq[1] << 8) |
-                   ((uint32_t)(uint8_t)(int8_t)c.nq[2] << 16) | ((uint32_t)code << 24);
-        double q0 = std::floor((lo[j] - (double)slo) / st), q1 = std::ceil((hi[j] - (double)slo) / st);
-        q0 = std::max(0.0, std::min(65535.0, q0));
-        q1 = std::max(0.0, std::min(65535.0, q1));
-        w.slab[j] = (uint32_t)q0 | ((uint32_t)q1 << 16);
-        const double sth = c.nosth || c.ts >= M_PI / 2 ? 1.0 : std::min(1.0, std::sin(c.ts) + 1e-12);
-        w.ext[j] = wq_code_lb(c.smin) | (wq_code_lb(c.s2) << 8) | (wq_code_ub(sth, WQ_UNIT) << 16) |
-                   (wq_code_ub(c.lmax, WQ_LEN) << 24);
-        double rho = 0.0;
-        if (c.leaf >= 0) {
-            double dlo[3], dhi[3];
-            decode(w, j, dlo, dhi);
-            const GNode& L = oct.nodes[(size_t)c.leaf];
-            for (int a = 0; a < 3; a++)
-                rho = std::max(rho, std::max(dlo[a] - (double)L.dn[a], (double)L.df[a] - dhi[a]));
-        }
-        w.ext2[j] = wq_code_ub(rho, WQ_LEN);
-    }
-    return w;
-}
-
-}  // namespace
-
 void build_wbvh_quick(const FlatOctree& oct, WBvh& out, bool tris)
 {
     const bool prof = std::getenv("RT_BUILD_PROFILE") != nullptr;
@@ -1559,7 +1257,7 @@ void build_wbvh_quick(const FlatOctree& oct, WBvh& out, bool tris)
                     ch[j].link = (uint32_t)P.a[j];
                 }
             }
-            out.nodes[(size_t)w] = q_node(ch, P.nc, oct);
+            out.nodes[(size_t)w] = q_node(ch, P.nc, oct.nodes.data());
             // the node's entry in its parent holds the axis boxes of the octree leaves below (rho = 0
             // there): its octree node's, and those of its leaf-run children (their record boxes can sit
             // an ulp inside the leaf's k-DOP, which the original vertices set)

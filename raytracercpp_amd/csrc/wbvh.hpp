@@ -211,16 +211,18 @@ struct WBvh {
 // product: the double products of floats are exact, each difference rounds once (2^-53 of the
 // larger term), so |ab x ac| >= |cross_double| - 2^-51 |ab| |ac|.  1 for a zero cross product
 // of non-zero edges is not claimed: 0 then (never skipped by the query's margins).
-inline double sin_at_a_lb(const GTri& t)
+// (host and device: the quick tree's builders, wbvh_quick.hpp)
+RT_HD double sin_at_a_lb(const GTri& t)
 {
     const double x0 = t.ab[0], x1 = t.ab[1], x2 = t.ab[2], y0 = t.ac[0], y1 = t.ac[1], y2 = t.ac[2];
     const double c0 = x1 * y2 - x2 * y1, c1 = x2 * y0 - x0 * y2, c2 = x0 * y1 - x1 * y0;
-    const double ab = std::sqrt(x0 * x0 + x1 * x1 + x2 * x2), ac = std::sqrt(y0 * y0 + y1 * y1 + y2 * y2);
+    const double ab = sqrt(x0 * x0 + x1 * x1 + x2 * x2), ac = sqrt(y0 * y0 + y1 * y1 + y2 * y2);
     const double lam = ab * ac;
     if (!(lam > 0x1p-100) || !(lam < 0x1p100))
         return 0.0;
-    const double c = std::sqrt(c0 * c0 + c1 * c1 + c2 * c2);
-    return std::max(0.0, (c - 0x1p-50 * lam) / lam * (1 - 1e-12));
+    const double c = sqrt(c0 * c0 + c1 * c1 + c2 * c2);
+    const double v = (c - 0x1p-50 * lam) / lam * (1 - 1e-12);
+    return 0.0 < v ? v : 0.0;   // (std::max(0.0, v))
 }
 
 // sin of the triangle's angle at a (Moller-Trumbore's vertex) as a float rounded down, from the

@@ -110,6 +110,13 @@ class Renderer:
         self._call("rt_get_device_builds", C.byref(n))
         return int(n.value)
 
+    def device_wide_builds(self) -> int:
+        """rt_get_device_wide_builds: quick wide BVHs built on the GPU (from a device-built octree) since the
+        renderer was created."""
+        n = C.c_int64()
+        self._call("rt_get_device_wide_builds", C.byref(n))
+        return int(n.value)
+
     # -- geometry (renderer.h:57-62) ------------------------------------------------
     def set_triangles(self, tri9, mat, uv6=None):
         tri9 = f32(tri9).reshape(-1, 9)

@@ -1,7 +1,8 @@
 """The blocking part of a geometry change on the C4 scene (sphere1m, default BVH settings), host octree
 build against the device build (rt_set_device_build), on the GPU: after rt_finish_accel,
 set_object_transform `repeats` times with a frame after each; per mode the medians of rt_stats build_ms,
-build_split_ms[0] (octree; a device build: with its readback), build_split_ms[3] (the rest of the upload)
+build_split_ms[0] (octree; a device build: with its readback), build_split_ms[3] (the quick wide BVH and
+the upload; in device mode the quick tree is built on the device too, rt_get_device_wide_builds counts it)
 and the wall time from the call to the image.  The background build of the frame before is waited for
 outside the timed part.  Mode off runs first, then mode on, in one process.
 Usage: python tools/rebuild_time.py [repeats]"""
@@ -39,8 +40,10 @@ for mode in ("host", "device"):
         print(json.dumps(samples[-1]), flush=True)
         r.finish_accel()
     builds = (r.stats()["host_builds"], r.device_builds())
+    wide_builds = r.device_wide_builds()
     rows[mode] = {k: statistics.median(x[k] for x in samples) for k in ("build_ms", "octree_ms", "upload_ms", "wall_ms")}
     rows[mode]["host_builds"], rows[mode]["device_builds"] = builds
+    rows[mode]["device_wide_builds"] = wide_builds
     rows[mode]["checksums"] = [x["checksum"] for x in samples]
     r.close()
 assert rows["host"].pop("checksums") == rows["device"].pop("checksums"), "the two modes' images differ"
