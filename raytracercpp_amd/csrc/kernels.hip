@@ -1017,12 +1017,16 @@ __device__ __forceinline__ bool wide_closest(const KParams& P, v3 o, v3 d, THit&
     using Stk = WStackLdsN<G == 1 ? CAP : W_STACK>;   // (a lane group's ring: W_STACK entries)
     WHit w;
     // a ray from the camera position reads the frame's camera risk keys
-    const uint64_t* rk = P.wrisk && o.x == P.cam_pos[0] && o.y == P.cam_pos[1] && o.z == P.cam_pos[2] ? P.wrisk : nullptr;
+    const bool cam = o.x == P.cam_pos[0] && o.y == P.cam_pos[1] && o.z == P.cam_pos[2];
+    const uint64_t* rk = P.wrisk && cam ? P.wrisk : nullptr;
     // the camera's risk cap: a ray into the silhouette's interior meets no at-risk triangle in case (b)
     const bool nob = rk && P.risk_cap && risk_cap_skip(P.risk_cap[0], P.cap_dir[0], d, W_QS_CLOSEST);
+    // the scene bound: the query of a camera ray whose line misses it would end after the root step with
+    // no child entered (wbvh.hpp wbvh_scene_bound); a wave whose lanes all miss it runs no step at all
+    int st = W_MISS;
     // (RT_COUNT builds pass no step limit, deliberately: they defer no query and count each to its end)
-    const int st = wide_run<Stk, G>(P, o, d, lv, w, INFINITY, true, W_QS_CLOSEST, rk, 0, 0.0f, RT_COUNT ? 0u : max_steps,
-                                    nob, 22);
+    if (!(cam && P.sb_valid && scene_bound_rejects(P.sb_lo, P.sb_hi, o, d)))
+        st = wide_run<Stk, G>(P, o, d, lv, w, INFINITY, true, W_QS_CLOSEST, rk, 0, 0.0f, RT_COUNT ? 0u : max_steps, nob, 22);
     if (max_steps && st == W_LONG) {   // (only a query with a step limit comes back long)
         *longq = true;
         return false;
@@ -3486,6 +3490,7 @@ __global__ __launch_bounds__(BLOCK, RT_OCC_PLAIN) void wide_query_kernel(KParams
     const uint64_t* rk = nullptr;
     int rsel = 0;
     float rsub = 0.0f, QS = W_QS_CLOSEST;
+    bool out = false;   // a camera ray outside the scene bound
     uint8_t sh = 2;
     if (kind == 2) {
         const v3 p = o, nrm = d, lp = mk(P.light[0], P.light[1], P.light[2]);
@@ -3505,8 +3510,9 @@ __global__ __launch_bounds__(BLOCK, RT_OCC_PLAIN) void wide_query_kernel(KParams
         bool s;
         if (P.wnodes && P.nnodes > 0 && P.seg_scale > 0.0f && !R0.nan && wide_shadow<G>(P, o, d, hi, p, lp, lv, &s, light))
             sh = s ? 1 : 0;
-    } else if (kind == 1 && P.wrisk && o.x == P.cam_pos[0] && o.y == P.cam_pos[1] && o.z == P.cam_pos[2]) {
+    } else if (kind == 1 && o.x == P.cam_pos[0] && o.y == P.cam_pos[1] && o.z == P.cam_pos[2]) {
         rk = P.wrisk;
+        out = P.sb_valid && scene_bound_rejects(P.sb_lo, P.sb_hi, o, d);   // (as wide_closest)
     }
     if (writer) {
         o_out[3 * i] = o.x;
@@ -3523,7 +3529,7 @@ __global__ __launch_bounds__(BLOCK, RT_OCC_PLAIN) void wide_query_kernel(KParams
     w.u = 1.0f;
     w.v = 0.0f;
     if (P.wnodes && P.nnodes > 0 && !ray_is_nan(o, d)) {
-        st = wide_run<WStackLds, G>(P, o, d, lv, w, INFINITY, true, QS, rk, rsel, rsub, 0u, false, -1);
+        st = out ? W_MISS : wide_run<WStackLds, G>(P, o, d, lv, w, INFINITY, true, QS, rk, rsel, rsub, 0u, false, -1);
         if (st == W_HIT) {
             uint4 M;
             if (wide_certified(P, w, o, d, M))

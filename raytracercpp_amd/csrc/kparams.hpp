@@ -65,6 +65,10 @@ struct KParams {
     // triangle at risk for the camera (sel 0) / the light (sel 1), computed with the words
     const float* risk_cap;
     float cap_dir[2][3];
+    // the scene bound (wbvh.hpp wbvh_scene_bound, of the resident wide BVH's root and cam_pos; sb_valid 0:
+    // none): a ray from cam_pos whose line misses [sb_lo, sb_hi] is a miss without a node load
+    float sb_lo[3], sb_hi[3];
+    int32_t sb_valid;
     // the origin cones (ocone.hpp; cells nullptr: none resident): the rays without risk words whose
     // ocone_skip holds skip case (b) (the reflection queries, ReflFeed)
     OConeView ocone;

@@ -99,6 +99,7 @@ Knobs Knobs::from_env()
     k.refl_shadow_sort = flag("RT_REFL_SHADOW_SORT", k.refl_shadow_sort);
     k.refl_sorted_frames = flag("RT_REFL_SORTED_FRAMES", k.refl_sorted_frames);
     k.risk_cap = flag("RT_RISK_CAP", k.risk_cap);
+    k.scene_bound = flag("RT_SCENE_BOUND", k.scene_bound);
     k.ocone = flag("RT_OCONE", k.ocone);
     k.ocone_dim = std::min(1024, std::max(1, num("RT_OCONE_DIM", k.ocone_dim)));
     k.inject_fail = num("RT_INJECT_FRAME_FAIL", 0);   // tests: the k-th ray_trace fails after its image start
@@ -753,6 +754,7 @@ int Renderer::poll_accel(bool wait, bool release)
         if (wide_ready_ && reserve_risk((size_t)wn) != RT_OK)
             return RT_EHIP;
         risk_valid_ = false;
+        sb_root_valid_ = false;
         risk_nodes_ = wn;
         risk_tris_ = wt;
         ++accel_ver_;
@@ -796,6 +798,7 @@ int Renderer::adopt_from_lead()
     if (geom_dirty_) {
         poll_accel(true, true);
         cones_ready_ = wide_ready_ = lslab_ready_ = ocone_ready_ = false;
+        sb_root_valid_ = false;
         auto t0 = std::chrono::steady_clock::now();
         oct_ = FlatOctree();   // (never built here)
         oct_nn_ = L.oct_nn_;
@@ -847,6 +850,7 @@ int Renderer::adopt_from_lead()
         lslab_ready_ = L.cones_ready_ && L.lslab_ready_;
         wide_ready_ = L.wide_ready_;
         risk_valid_ = false;
+        sb_root_valid_ = false;
         risk_nodes_ = L.risk_nodes_;
         risk_tris_ = L.risk_tris_;
         mir_accel_ = L.accel_ver_;
@@ -1064,6 +1068,7 @@ int Renderer::ensure_device_scene()
         // a build of the previous geometry reads oct_: let it finish (its result is dropped)
         poll_accel(true, true);
         cones_ready_ = wide_ready_ = lslab_ready_ = ocone_ready_ = false;
+        sb_root_valid_ = false;
         using clk = std::chrono::steady_clock;
         auto ms_since = [](clk::time_point t) { return std::chrono::duration<float, std::milli>(clk::now() - t).count(); };
         auto t0 = clk::now();
@@ -1163,6 +1168,7 @@ int Renderer::ensure_device_scene()
             if (rc != RT_OK)
                 return rc;
             risk_valid_ = false;
+            sb_root_valid_ = false;
             risk_nodes_ = wn;
             risk_tris_ = wt;
             ++accel_ver_;
@@ -2309,6 +2315,26 @@ int Renderer::prepare_risk(KParams& P, hipStream_t stream)
     P.risk_nl = 0.0f;
     P.risk_nu = 0.0f;
     P.risk_cap = nullptr;
+    // the scene bound (wbvh.hpp wbvh_scene_bound) of the resident tree's root for this launch's camera: the
+    // root is the host copy's, or read back once per adopted tree where the tree was built on the device
+    // (or copied from the lead device); the six floats travel by value with each launch.  RT_SCENE_BOUND=0: none
+    P.sb_valid = 0;
+    if (P.wnodes && knobs_.scene_bound && risk_nodes_ > 0) {
+        if (!sb_root_valid_) {
+            if (!wb_on_device_ && !lead_ && !wb_.nodes.empty())
+                sb_root_ = wb_.nodes[0];
+            else {
+                const hipError_t e = hipMemcpy(&sb_root_, d_wnodes_.p, sizeof(WNode), hipMemcpyDeviceToHost);
+                if (e != hipSuccess)
+                    return hip_fail(e, "download (the wide BVH's root)");
+            }
+            sb_root_valid_ = true;
+        }
+        const WSceneBound B = wbvh_scene_bound(sb_root_, P.cam_pos, P.light, P.scene_scale, W_QS_CLOSEST);
+        std::memcpy(P.sb_lo, B.lo, sizeof P.sb_lo);
+        std::memcpy(P.sb_hi, B.hi, sizeof P.sb_hi);
+        P.sb_valid = B.valid;
+    }
     if (!P.wnodes || !knobs_.risk || risk_nodes_ <= 0 || !d_wrisk_.p || !d_wlinks_.p)
         return RT_OK;
     // the risk caps' directions: from the camera / the light towards the scene's centre (any direction is

@@ -90,6 +90,8 @@ struct Knobs {
                               // instead of a sorted copy (kernels.hip refl_sort_frames_kernel)
     bool risk_cap = true;     // RT_RISK_CAP=0: no risk caps (camera / shadow rays into a silhouette's interior skip
                               // case (b), wbvh.hpp risk_cap_skip)
+    bool scene_bound = true;  // RT_SCENE_BOUND=0: no scene bound (camera rays that miss the root's widened frame
+                              // still run their root step, wbvh.hpp wbvh_scene_bound)
     bool ocone = true;        // RT_OCONE=0: no origin cones (reflection queries always run case (b), ocone.hpp)
     int ocone_dim = 128;      // RT_OCONE_DIM=n: the origin-cone grid's cells along the scene's longest axis
     int inject_fail = 0;      // RT_INJECT_FRAME_FAIL=k (tests): the k-th ray_trace fails after its image start
@@ -355,6 +357,9 @@ private:
     // and the camera / light / structure they were computed for; risk_ev_ follows their launch
     DevBuf d_wlinks_, d_wrisk_;
     bool risk_valid_ = false;
+    // the resident wide BVH's root, for the scene bound (prepare_risk); false after every change of tree
+    WNode sb_root_{};
+    bool sb_root_valid_ = false;
     int64_t risk_nodes_ = 0, risk_tris_ = 0;   // the resident wide BVH's node and triangle counts
     float risk_cam_[3] = {0, 0, 0}, risk_light_[3] = {0, 0, 0};
     float risk_G_ = 0.0f, risk_nl_ = 0.0f, risk_nu_ = 0.0f;

@@ -535,6 +535,160 @@ RT_HD float wq_eta(const WReach& r, float L, float D)
     return n2 * __builtin_fmaf(2.0f, x, 1.0f) * (1.0f + 0x1p-16f);
 }
 
+// The closed-form reach of a well-conditioned child (W_FAST_REACH, DESIGN.md 5.6 "Closed-form reach"): at
+// fixed qa and smin, E, Rlat, Rpar and eta above are linear in (L, D) (E's numerator is, its factor is a
+// constant, and the others are linear in L, D and E), and every term falls as qa or smin grows.  So for qa
+// >= W_FAST_Q and smin >= W_FAST_S each is at most its value at that corner:
+//   E <= u (143.9 L + 45.6 D), Rlat <= u (156.1 L + 15.42 D), Rpar <= u (0.00013 L + 30.25 D),
+//   eta <= u (45.65 L + 9.08 D)                                            (W_FAST_Q = W_FAST_S = 1/4),
+// the float functions' values at (L, D) = (1, 0) and (0, 1) (143.778, 45.534; 155.898, 15.4008; 0.000121,
+// 30.2129; 45.6016, 9.06235) rounded up by 2^-10 or more, which covers the float evaluation of either
+// side.  tests/c/wq_fast_bound.cpp compares them with the functions over every smin code from the
+// threshold up, every finite L code, qa from W_FAST_Q to 1 and D over 2^-20 .. 2^20.  The child's smin
+// byte is compared raw (the code is monotone); qlb, not qa, is compared, so QS plays no part.
+// Off by default: with it the plain frame kernel spills 5 VGPRs at its 168 against 2 without.
+#ifndef W_FAST_REACH
+#define W_FAST_REACH 0
+#endif
+#define W_FAST_Q 0.25f
+#define W_FAST_S 0.25f
+// the smallest smin code whose value is >= W_FAST_S (wq_val: an octave per 8 codes, 255 = 1)
+constexpr uint32_t W_FAST_S_CODE = ((__builtin_bit_cast(uint32_t, W_FAST_S) - WQ_UNIT) + 0xFFFFFu) >> 20;
+static_assert(W_FAST_S_CODE == 239u, "the closed form's constants are those of smin = 1/4");
+// e: the child's ext word (smin code in byte 0, L code in byte 3)
+RT_HD bool wq_fast_ok(float qlb, uint32_t e)
+{
+    return W_FAST_REACH && qlb >= W_FAST_Q && (e & 0xffu) >= W_FAST_S_CODE && (e >> 24) != 255u;
+}
+RT_HD void wq_fast(float L, float D, float& E, float& Rlat, float& Rpar)
+{
+    const float UL = 0x1p-24f * L, UD = 0x1p-24f * D;
+    E = __builtin_fmaf(143.9f, UL, 45.6f * UD);
+    Rlat = __builtin_fmaf(156.1f, UL, 15.42f * UD);
+    Rpar = __builtin_fmaf(0.00013f, UL, 30.25f * UD);
+}
+RT_HD float wq_fast_eta(float L, float D)
+{
+    return __builtin_fmaf(45.65f * 0x1p-24f, L, 9.08f * 0x1p-24f * D);
+}
+
+// The scene bound (DESIGN.md 5.6 "The scene bound"): a box such that a camera ray whose LINE misses it
+// enters no child of the root, so its query ends after the root step as W_MISS; such a ray is answered
+// W_MISS without loading a node (kernels.hip wide_closest).  The box is the union U of the root's non-empty
+// children's decoded boxes [origin + q_lo step, origin + q_hi step], widened per axis by W >= every
+// widening the root step applies to a child's box for a ray from cam:
+//   (a) Rb + dtp |d_axis| <= m + Rlat + Rpar (1 + 2^-16) (wbvh_closest: the box widened by Rb = m + Rlat,
+//       then tmin -= dtp, tmax += dtp with dtp = Rpar idl, idl <= (1 + 2^-17) / |d| <= (1 + 2^-16) /
+//       |d_axis|), Rlat / Rpar from wq_reach / wq_split at qa = QS: the query's qa = max(qlb, QS) and
+//       every term falls as qa grows; D = the query's Dn for cam (a per-child D is smaller);
+//   (b) without risk words, the child's box widened by m + rho; with them, its at-risk box widened by m +
+//       rho: the octree leaves it covers lie within rho of the child's box (ext2; check_wbvh), and its
+//       bytes are rounded outward by less than a step (wrisk_qbox), so it lies within rho + step of the
+//       child's box: 2 rho + step + m in all.  Case (b) accepts any t: hence the line test, not the ray's.
+// (The root's whole frame [origin, origin + 255 step] would serve as well, but its power-of-two step makes
+// it up to twice the scene: from the C4 camera it fills the view, and nothing would be rejected.)
+// The slab and the cone only remove children.  The reach functions are the query's own float code (the
+// device's reciprocal and square root differ from the host's by 1 ulp); the sum is taken in double, 1/8 m
+// and a relative 2^-19 cover the two roundings of each plane's t on either side (each a relative 2^-24
+// of |origin - o| + W over |d_axis|, against m = 2^-16 (max|o| + S)), and the planes are rounded outward
+// to float.  valid = 0 (nothing is rejected): a child with no finite reach (L code 255, beta > 1/2, X <=
+// 0) or rho, a scale outside the query's gate, a non-finite frame, camera or light (wbvh_risk_args then
+// marks every child at risk over its whole frame).  scale (tests): the box shrunk about its centre.
+struct WSceneBound {
+    float lo[3], hi[3];
+    int32_t valid;
+};
+
+inline WSceneBound wbvh_scene_bound(const WNode& root, const float cam[3], const float* light, float S, float QS,
+                                    double scale = 1.0)
+{
+    WSceneBound B{};
+    const float om = fmaxf(fabsf(cam[0]), fmaxf(fabsf(cam[1]), fabsf(cam[2])));
+    if (!(om < 0x1p26f) || !(S > 0x1p-20f && S < 0x1p20f))
+        return B;
+    if (light && !(std::isfinite(light[0]) && std::isfinite(light[1]) && std::isfinite(light[2])))
+        return B;
+    const float m = 0x1p-16f * (om + S);   // kernels.hip wide_margin
+    const float org[3] = {root.ox, root.oy, root.oz};
+    float st[3], f2 = 0.0f, smax = 0.0f;
+    for (int a = 0; a < 3; a++) {
+        st[a] = __builtin_bit_cast(float, ((root.exps >> (8 * a)) & 0xffu) << 23);
+        smax = fmaxf(smax, st[a]);
+        const float Da = org[a] - cam[a];
+        const float f = fmaxf(fabsf(Da), fabsf(__builtin_fmaf(255.0f, st[a], Da)));
+        f2 = a == 0 ? f * f : f2 + f * f;   // (fx fx + fy fy) + fz fz, as the query's Dn
+    }
+    const float Dn = std::sqrt(f2) * (1.0f + 0x1p-16f) + m;
+    if (!(Dn < 0x1p28f))
+        return B;   // (a NaN or infinite frame as well)
+    const float D = Dn * (1.0f + 0x1p-20f);
+    double W = 0.0;
+    int qlo[3] = {255, 255, 255}, qhi[3] = {0, 0, 0};
+    bool any = false;
+    for (int j = 0; j < W_WIDTH; j++) {
+        if (root.child[j] == W_EMPTY)
+            continue;
+        any = true;
+        const uint32_t e = root.ext[j];
+        if ((e >> 24) == 255u)
+            return B;
+        const float smin = fmaxf(wq_val_nz(e & 0xffu, WQ_UNIT), W_SMIN_FLOOR);
+        const float L = wq_val_nz(e >> 24, WQ_LEN);
+        const WReach wr = wq_reach(QS, smin, L, D);
+        float Rlat, Rpar;
+        wq_split(wr, L, D, Rlat, Rpar);
+        const float rho = wq_len(root.ext2[j] & 0xffu);
+        if (!(wr.E < INFINITY) || !(Rlat < INFINITY) || !(Rpar < INFINITY) || !(rho < INFINITY))
+            return B;
+        const double rs = std::max(1.0, (double)W_R_SCALE);
+        W = std::max(W, std::max(rs * ((double)Rlat + (double)Rpar * (1.0 + 0x1p-16)), 2.0 * (double)rho + (double)smax));
+        for (int a = 0; a < 3; a++) {
+            qlo[a] = std::min(qlo[a], (int)root.qlo[a][j]);
+            qhi[a] = std::max(qhi[a], (int)root.qhi[a][j]);
+        }
+    }
+    if (!any)
+        return B;
+    W = (W + 1.125 * (double)m) * (1.0 + 0x1p-19);
+    for (int a = 0; a < 3; a++) {
+        const double l = (double)org[a] + qlo[a] * (double)st[a] - W, h = (double)org[a] + qhi[a] * (double)st[a] + W;
+        const double c = 0.5 * (l + h), r = 0.5 * (h - l) * scale;
+        const double lo = c - r, hi = c + r;
+        if (!(std::fabs(lo) < 0x1p27) || !(std::fabs(hi) < 0x1p27) || !(lo <= hi))
+            return B;
+        B.lo[a] = (float)lo;
+        if ((double)B.lo[a] > lo)
+            B.lo[a] = std::nextafter(B.lo[a], -INFINITY);
+        B.hi[a] = (float)hi;
+        if ((double)B.hi[a] < hi)
+            B.hi[a] = std::nextafter(B.hi[a], INFINITY);
+    }
+    B.valid = 1;
+    return B;
+}
+
+// The per-ray test: true when the line o + t d misses the box [lo, hi], by the slab arithmetic of
+// wbvh_closest's box() (the same reciprocals, DMIN clamp and SL slack; o, lo and hi are finite and below
+// 2^27, wbvh_scene_bound).  A direction with a NaN or infinite component, or shorter than 2^-50 (the
+// query's idl then exceeds the bound's 1 / |d_axis|), is never rejected.
+RT_HD bool scene_bound_rejects(const float lo[3], const float hi[3], v3 o, v3 d)
+{
+    const float DMIN = 0x1p-100f;
+    constexpr float SL = 0x1p-20f;
+    const float dd = d.x * d.x + d.y * d.y + d.z * d.z;
+    if (!(dd >= 0x1p-100f && dd < INFINITY))
+        return false;
+    const float ix = 1.0f / (fabsf(d.x) < DMIN ? copysignf(DMIN, d.x) : d.x);
+    const float iy = 1.0f / (fabsf(d.y) < DMIN ? copysignf(DMIN, d.y) : d.y);
+    const float iz = 1.0f / (fabsf(d.z) < DMIN ? copysignf(DMIN, d.z) : d.z);
+    const float x0 = (lo[0] - o.x) * ix, x1 = (hi[0] - o.x) * ix;
+    const float y0 = (lo[1] - o.y) * iy, y1 = (hi[1] - o.y) * iy;
+    const float z0 = (lo[2] - o.z) * iz, z1 = (hi[2] - o.z) * iz;
+    const float tmin = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fminf(z0, z1));
+    const float tmax = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fmaxf(z0, z1));
+    return tmin > __builtin_fmaf(fabsf(tmax), SL, tmax);
+}
+
 // A frame's two risk points (kernels.hip wide_risk_kernel): sel 0 the camera (rays start at it), sel
 // 1 the light (shadow rays: o = p + 1e-4 n, d = normalize(light - p), renderer.cpp:340-402, for hit
 // points p in the scene box [lo, hi]).  The shadow rays that may use the light's keys are the ones
@@ -1090,12 +1244,20 @@ RT_HD int wbvh_closest(const WNode* nodes, const GTri* tris, v3 o, v3 d, float m
                     // Moller-Trumbore's reports, D = Dn)
 #if W_SOUND_A
                     const float Da = W_A_CHILD_D ? dchild() : Dn;
-                    const WReach wr = wq_reach(qa, smin, L, Da);
-                    const float R = __builtin_fmaf(W_R_SCALE, wr.E, m);
+                    // (a well-conditioned child seen at cos >= W_FAST_Q: the bounds' closed form, wq_fast)
+                    const bool fastr = wq_fast_ok(qlb, e);
+                    WReach wr;
                     // the box test: the line crosses the box widened by the lateral reach, and a report lies
                     // within Rpar of that crossing along the line (wq_split)
-                    float Rlat, Rpar;
-                    wq_split(wr, L, Da, Rlat, Rpar);
+                    float E, Rlat, Rpar;
+                    if (fastr)
+                        wq_fast(L, Da, E, Rlat, Rpar);
+                    else {
+                        wr = wq_reach(qa, smin, L, Da);
+                        E = wr.E;
+                        wq_split(wr, L, Da, Rlat, Rpar);
+                    }
+                    const float R = __builtin_fmaf(W_R_SCALE, E, m);
                     const float Rb = __builtin_fmaf(W_R_SCALE, Rlat, m);
                     const float dtp = W_R_SCALE * Rpar * idl;
 #else
@@ -1129,7 +1291,7 @@ RT_HD int wbvh_closest(const WNode* nodes, const GTri* tris, v3 o, v3 d, float m
                         // N . (o + t d - origin) in [C0, C1] widened by w: t between
                         // (C0 - w + b) / a and (C1 + w + b) / a
 #if W_SOUND_A
-                        const float eta = wq_eta(wr, L, Da);
+                        const float eta = fastr ? wq_fast_eta(L, Da) : wq_eta(wr, L, Da);
 #else
                         const float eta = 0.0f;
 #endif
