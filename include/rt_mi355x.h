@@ -195,6 +195,25 @@ int rt_wbvh_quick_build_device(int32_t device, const float *tri9, int64_t n, int
                                int32_t leaf_max_obj_count, uint64_t digest[6], int64_t stats[5], int64_t check[4],
                                float ms[2]);
 
+/* Object edits on the device.  With the device build on, rt_set_object_transform on a
+ * handle whose positions are resident from the build before (not a helper of rt_set_devices) queues
+ * its matrix; before the next build, or the next host reader of the positions (a host build,
+ * brute-force mode, rt_get_triangles, a helper's copy), the queue runs on the GPU over the resident
+ * positions in place, one launch per call in call order (geom_gpu.hip: Transform::operator()(Point),
+ * mat.cpp:83-100, the host's expression: the same bytes), instead of a host pass and a new upload.
+ * A non-finite result is reported by the next frame as the host path reports it (RT_EINVAL).
+ * RT_GPU_XFORM=0 at rt_create keeps the host pass.  rt_get_device_transforms: the matrices applied
+ * by the kernel since rt_create. */
+int rt_get_device_transforms(rt_renderer *r, int64_t *count);
+
+/* The kernel alone: uploads pts ([n][3]) to 'device', runs it with m and copies the points back into
+ * out (which may be pts); *nonfinite = 1 when a written coordinate is not finite, else 0; ms
+ * (optional) = {the kernel by HIP events, the whole call on the host clock}.  Against
+ * rt_transform_points the bytes differ only where both are NaN (sign and payload).  RT_EINVAL for a
+ * null pointer or n < 0; RT_EHIP (rt_last_error) without a usable device; n == 0: RT_OK, no launch. */
+int rt_transform_points_device(int32_t device, const float m[16], const float *pts, int64_t n, float *out,
+                               int32_t *nonfinite, float ms[2]);
+
 /* Single-process multi-device rendering (no reference counterpart: the reference renders on
  * one host, RenderThread::run, QT/mainWindowThreads.cpp:39-65).  ids[0] must be the handle's
  * device; n = 0 (or ids NULL) returns to one device.  rt_render then renders on every device
@@ -261,6 +280,11 @@ int rt_set_camera_lens(rt_renderer *r, float fov, float aspect);
 /* Renderer::set_object_transform / reset_previous_transform (renderer.cpp:212-224) */
 int rt_set_object_transform(rt_renderer *r, const float m[16]);
 int rt_reset_previous_transform(rt_renderer *r);
+/* Renderer::_triangles' positions as rt_set_object_transform left them (renderer.cpp:214-224: every
+ * vertex through object_transform x previous^-1): *n = the triangle count, and with tri9 != NULL the
+ * world-space positions [n][9] in caller order, after every transform so far (object edits still
+ * queued for the device, below, are applied first).  The same bytes in both build modes. */
+int rt_get_triangles(rt_renderer *r, float *tri9, int64_t *n);
 
 /* Renderer::set_*_map / set_skysphere and clear_*_map (renderer.cpp:192-205).
  * rgba: w*h*4 floats (Image texels); NULL clears the slot. */

@@ -102,6 +102,9 @@ SIGNATURES = {
     "rt_get_camera_matrices": (C.c_int, [_H, _f32p, _f32p, _f32p]),
     "rt_set_object_transform": (C.c_int, [_H, _f32p]),
     "rt_reset_previous_transform": (C.c_int, [_H]),
+    "rt_get_triangles": (C.c_int, [_H, _f32p, _i64p]),
+    "rt_get_device_transforms": (C.c_int, [_H, _i64p]),
+    "rt_transform_points_device": (C.c_int, [C.c_int32, _f32p, _f32p, C.c_int64, _f32p, _i32p, _f32p]),
     "rt_set_texture": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, _f32p]),
     "rt_set_skybox": (C.c_int, [_H, _i32p, _i32p, C.POINTER(_f32p)]),
     "rt_reconstruct_bvh_new": (C.c_int, [_H]),
@@ -250,6 +253,20 @@ def transform_points(m, pts):
     out = np.zeros_like(pts)
     lib().rt_transform_points(ptr(m, _f32p), ptr(pts, _f32p), pts.shape[0], ptr(out, _f32p))
     return out
+
+
+def transform_points_device(m, pts, device=0):
+    """rt_transform_points_device: (points, nonfinite flag, (kernel ms by HIP events, whole call ms)) of
+    the object-edit kernel alone on the GPU; against transform_points the bytes differ only where both
+    are NaN.  Raises RtError (RT_EHIP: no usable device)."""
+    m = f32(m)
+    pts = f32(pts).reshape(-1, 3)
+    out = np.zeros_like(pts)
+    flag = C.c_int32()
+    ms = np.zeros(2, np.float32)
+    check(lib().rt_transform_points_device(device, ptr(m, _f32p), ptr(pts, _f32p), pts.shape[0], ptr(out, _f32p),
+                                           C.byref(flag), ptr(ms, _f32p)), "rt_transform_points_device")
+    return out, int(flag.value), (float(ms[0]), float(ms[1]))
 
 
 def load_obj(path, xform, mat_offset=0):

@@ -9,6 +9,7 @@
 
 #include "../../include/rt_mi355x_diag.h"   // (includes rt_mi355x.h)
 #include "host_scene.hpp"
+#include "launch.hpp"
 #include "octree.hpp"
 #include "octree_gpu.hpp"
 #include "ocone.hpp"
@@ -896,6 +897,77 @@ int rt_get_device_wide_builds(rt_renderer* r, int64_t* count)
         *count = R(r)->device_wide_builds();
         return RT_OK;
     });
+}
+
+// Renderer::_triangles (renderer.cpp:214-224)
+int rt_get_triangles(rt_renderer* r, float* tri9, int64_t* n)
+{
+    return guarded(R(r), [&] { return R(r)->get_triangles(tri9, n); });
+}
+
+int rt_get_device_transforms(rt_renderer* r, int64_t* count)
+{
+    return guarded(R(r), [&] {
+        if (!count)
+            return RT_EINVAL;
+        *count = R(r)->device_transforms();
+        return RT_OK;
+    });
+}
+
+int rt_transform_points_device(int32_t device, const float m[16], const float* pts, int64_t n, float* out,
+                               int32_t* nonfinite, float ms[2])
+{
+    if (n < 0 || !m || !pts || !out || !nonfinite)
+        return bad("rt_transform_points_device: bad arguments");
+    auto t0 = std::chrono::steady_clock::now();
+    *nonfinite = 0;
+    if (ms)
+        ms[0] = ms[1] = 0.0f;
+    if (n == 0)
+        return RT_OK;
+    auto hip_bad = [](hipError_t e, const char* what) {
+        g_err = std::string("rt_transform_points_device: ") + what + ": " + hipGetErrorString(e);
+        return RT_EHIP;
+    };
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess)
+        return hip_bad(e, "hipSetDevice");
+    rt::DevBuf d_pts, d_flag;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    struct EvGuard {
+        hipEvent_t* ev;
+        ~EvGuard()
+        {
+            for (int i = 0; i < 2; i++)
+                if (ev[i]) (void)hipEventDestroy(ev[i]);
+        }
+    } guard{ev};
+    const size_t bytes = (size_t)n * 12;
+    if ((e = d_pts.reserve(bytes)) != hipSuccess || (e = d_flag.reserve(4)) != hipSuccess ||
+        (e = hipEventCreate(&ev[0])) != hipSuccess || (e = hipEventCreate(&ev[1])) != hipSuccess)
+        return hip_bad(e, "allocation");
+    if ((e = hipMemcpy(d_pts.p, pts, bytes, hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemset(d_flag.p, 0, 4)) != hipSuccess)
+        return hip_bad(e, "upload");
+    if ((e = hipEventRecord(ev[0], nullptr)) != hipSuccess)
+        return hip_bad(e, "hipEventRecord");
+    if ((e = rt_launch_xform_points(m, d_pts.as<float>(), n, d_flag.as<uint32_t>(), nullptr)) != hipSuccess)
+        return hip_bad(e, "launch");
+    float dev_ms = 0.0f;
+    if ((e = hipEventRecord(ev[1], nullptr)) != hipSuccess || (e = hipEventSynchronize(ev[1])) != hipSuccess ||
+        (e = hipEventElapsedTime(&dev_ms, ev[0], ev[1])) != hipSuccess)
+        return hip_bad(e, "kernel");
+    uint32_t word = 0;
+    if ((e = hipMemcpy(out, d_pts.p, bytes, hipMemcpyDeviceToHost)) != hipSuccess ||
+        (e = hipMemcpy(&word, d_flag.p, 4, hipMemcpyDeviceToHost)) != hipSuccess)
+        return hip_bad(e, "readback");
+    *nonfinite = word != 0;
+    if (ms) {
+        ms[0] = dev_ms;
+        ms[1] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return RT_OK;
 }
 
 int rt_wbvh_quick_digest(const float* tri9, int64_t n, int32_t max_depth, int32_t leaf_max_obj_count, uint64_t digest[6],

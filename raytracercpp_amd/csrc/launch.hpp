@@ -60,6 +60,10 @@ RT_LAUNCH rt_launch_ocone(const rt::OConeEnt* E, const rt::GTri* tris, const uin
                           const int32_t dim[3], double h, double r, double slack, double QS, double cos_cap,
                           uint2* cells, size_t ncells, hipStream_t stream);
 
+// geometry edits (geom_gpu.hip): xform_point over pts [n][3] in place; *nonfinite |= 1 when a written
+// coordinate is not finite.  n <= 0: no launch
+RT_LAUNCH rt_launch_xform_points(const float m[16], float* pts, int64_t n, uint32_t* nonfinite, hipStream_t stream);
+
 // the reflection engine (renderer.cpp drives the levels)
 RT_LAUNCH rt_launch_refl_level0(const rt::KParams* P, rt::FrameRec* fr1, unsigned int* nfr1, hipStream_t stream);
 RT_LAUNCH rt_launch_refl_stage(rt::ReflStage stage, const rt::KParams* P, const rt::ReflArgs* A, hipStream_t stream);

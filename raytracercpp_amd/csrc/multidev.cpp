@@ -120,7 +120,7 @@ int Renderer::set_devices(const int* ids, int n)
 
 // The helpers' copy of the lead's scene: the small state every frame, geometry / materials /
 // textures when the lead's versions moved (each change there bumps one).
-void Renderer::mirror_from(const Renderer& L)
+int Renderer::mirror_from(Renderer& L)
 {
     if (knobs_.exact != L.knobs_.exact)
         set_exact(L.knobs_.exact);
@@ -139,7 +139,12 @@ void Renderer::mirror_from(const Renderer& L)
     shape_ = L.shape_;
     shape_mat_ = L.shape_mat_;
     if (mir_geom_ != L.geom_ver_) {
+        // (the lead's positions may live on its device: object edits there leave its tri_ stale)
+        int rc = L.host_tris();
+        if (rc != RT_OK)
+            return rc;
         tri_ = L.tri_;
+        drop_device_positions();
         tri_mat_ = L.tri_mat_;
         tri_mat_lo_ = L.tri_mat_lo_;
         tri_mat_hi_ = L.tri_mat_hi_;
@@ -147,7 +152,6 @@ void Renderer::mirror_from(const Renderer& L)
         std::memcpy(prev_object_, L.prev_object_, sizeof(prev_object_));
         has_bvh_ = L.has_bvh_;
         geom_dirty_ = true;
-        tri9_dirty_ = true;
         mir_geom_ = L.geom_ver_;
     }
     if (mir_mats_ != L.mats_ver_) {
@@ -163,6 +167,7 @@ void Renderer::mirror_from(const Renderer& L)
         tex_dirty_ = true;
         mir_tex_ = L.tex_ver_;
     }
+    return RT_OK;
 }
 
 // render(Renderer&) over the devices of rt_set_devices: every rank renders its bands
@@ -189,7 +194,9 @@ int Renderer::render_multi()
     if ((e = M.gather.reserve(chunk * n)) != hipSuccess) return hip_fail(e, "hipMalloc (gather)");
     for (int i = 1; i < n; i++) {
         Renderer& h = *M.helpers[i - 1];
-        h.mirror_from(*this);
+        int rcm = h.mirror_from(*this);
+        if (rcm != RT_OK)
+            return rcm;
         if ((e = hipSetDevice(M.ids[i])) != hipSuccess || (e = M.bands[i - 1]->reserve(chunk)) != hipSuccess)
             return hip_fail(e, "hipMalloc (band buffer)");
     }

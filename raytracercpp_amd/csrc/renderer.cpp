@@ -105,6 +105,7 @@ Knobs Knobs::from_env()
     k.inject_fail = num("RT_INJECT_FRAME_FAIL", 0);   // tests: the k-th ray_trace fails after its image start
     k.async_accel = on("RT_ASYNC_ACCEL", true);
     k.gpu_build = flag("RT_GPU_BUILD", k.gpu_build);
+    k.gpu_xform = on("RT_GPU_XFORM", true);
     k.accel_hold = flag("RT_ACCEL_HOLD", k.accel_hold);
     const int chunk = num("RT_REFL_CHUNK_LOG2", k.refl_chunk_log2);
     if (chunk >= 10 && chunk <= 27)   // small values (tests): many chunks per level
@@ -247,6 +248,7 @@ int Renderer::set_triangles(const float* tri9, const int32_t* mat, const float* 
     if (n >= (int64_t)1 << 30)
         return fail(RT_EUNSUPPORTED, "set_triangles: more than 2^30 triangles");
     tri_.assign(tri9, tri9 + 9 * n);
+    drop_device_positions();
     tri_mat_.assign(mat, mat + n);
     // the material range, checked by validate() before every launch without re-reading
     // the per-triangle indices (a 1M-triangle scan per frame cost ~0.2 ms of host time)
@@ -291,6 +293,7 @@ int Renderer::add_plane(float px, float py, float pz, float nx, float ny, float 
 int Renderer::clear_geometry()
 {
     tri_.clear();
+    drop_device_positions();
     tri_mat_.clear();
     tri_mat_lo_ = INT32_MAX;
     tri_mat_hi_ = INT32_MIN;
@@ -400,16 +403,32 @@ void Renderer::get_camera_matrices(float pos[3], float proj_inv[16], float c2w[1
 
 // renderer.cpp:214-224: every triangle goes through object_transform * previous^-1,
 // then the BVH is rebuilt.
+// With the device build on and the positions resident (d_tri9_), the matrix is queued for the device
+// (apply_device_edits, before the next build or host reader) and tri_ is left stale.
 int Renderer::set_object_transform(const float m[16])
 {
+    const bool on_device = knobs_.gpu_build && knobs_.gpu_xform && !lead_ && tri9_current_;
+    if (!on_device) {
+        int rc = host_tris();
+        if (rc != RT_OK)
+            return rc;
+    }
     float inv[16], t[16];
     mat::inverse(prev_object_, inv);
     std::memcpy(prev_object_, inv, sizeof(inv));
     mat::compose(m, prev_object_, t);
-    size_t n = tri_.size() / 3;
-    std::vector<float> out(tri_.size());
-    mat::transform_points(t, tri_.data(), (int64_t)n, out.data());
-    tri_.swap(out);
+    if (on_device) {
+        std::array<float, 16> q;
+        std::memcpy(q.data(), t, sizeof(t));
+        pending_xf_.push_back(q);
+        tri_stale_ = true;
+    } else {
+        size_t n = tri_.size() / 3;
+        std::vector<float> out(tri_.size());
+        mat::transform_points(t, tri_.data(), (int64_t)n, out.data());
+        tri_.swap(out);
+        drop_device_positions();
+    }
     has_bvh_ = true;
     geom_dirty_ = true, ++geom_ver_;
     std::memcpy(prev_object_, m, sizeof(prev_object_));
@@ -817,7 +836,6 @@ int Renderer::adopt_from_lead()
         if (e != hipSuccess)
             return hip_fail(e, "rt_set_devices: scene copy from the lead device");
         geom_dirty_ = false;
-        tri9_dirty_ = true;
         mir_accel_ = ~0ull;
         build_ms_ = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
         build_split_ms_[0] = build_split_ms_[1] = build_split_ms_[2] = 0.0f;
@@ -890,7 +908,6 @@ int Renderer::build_octree_device(int64_t n, bool& built)
     if ((e = pin(RING * CHUNK)) != hipSuccess || (e = d_tri9_.reserve(in_bytes)) != hipSuccess ||
         (e = d_oct_info_.reserve(sizeof(OctreeDevInfo))) != hipSuccess)
         return hip_fail(e, "hipMalloc (device octree build)");
-    tri9_dirty_ = true;   // (the raster path uploads its own copy)
     char* ring = static_cast<char*>(build_pin_);
     hipEvent_t ev[RING] = {};
     struct EvGuard {
@@ -902,9 +919,11 @@ int Renderer::build_octree_device(int64_t n, bool& built)
         }
     } guard{ev};
     for (int i = 0; i < RING && e == hipSuccess; i++) e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
-    // staging: the host fills one chunk of the ring while the DMA takes the one before
+    // staging: the host fills one chunk of the ring while the DMA takes the one before (not when the
+    // positions are resident already: a build before this one, or a device transform, left them there)
+    const bool staged = !tri9_current_;
     const char* src = reinterpret_cast<const char*>(tri_.data());
-    for (size_t i = 0, off = 0; e == hipSuccess && off < in_bytes; i++, off += CHUNK) {
+    for (size_t i = 0, off = 0; staged && e == hipSuccess && off < in_bytes; i++, off += CHUNK) {
         const size_t len = std::min(CHUNK, in_bytes - off);
         if (i >= RING)
             e = hipEventSynchronize(ev[i % RING]);   // the slot's last upload has left it
@@ -919,6 +938,7 @@ int Renderer::build_octree_device(int64_t n, bool& built)
         (void)hipStreamSynchronize(stream_);
         return hip_fail(e, "upload (device octree build)");
     }
+    tri9_current_ = true;   // (in stream order: every later reader of d_tri9_ follows stream_ or waits for it)
     if (!oct_dev_info_)
         oct_dev_info_ = std::make_unique<OctreeDevInfo>();
     OctreeDevInfo& info = *oct_dev_info_;
@@ -1052,6 +1072,76 @@ int Renderer::host_wide()
     return RT_OK;
 }
 
+// The queued object edits (set_object_transform with the device build on), applied to d_tri9_ where it
+// lies: one launch per matrix on stream_, in call order, then the kernel's word.
+int Renderer::apply_device_edits()
+{
+    if (pending_xf_.empty())
+        return RT_OK;
+    hipError_t e = hipSetDevice(device_);
+    if (e != hipSuccess)
+        return hip_fail(e, "hipSetDevice");
+    // raster frames in flight on other streams read d_tri9_
+    if (sync_slots() != RT_OK)
+        return RT_EHIP;
+    if ((e = d_geom_flag_.reserve(4)) != hipSuccess)
+        return hip_fail(e, "hipMalloc (object transform)");
+    const int64_t npts = (int64_t)(tri_.size() / 3);
+    e = hipMemsetAsync(d_geom_flag_.p, 0, 4, stream_);
+    size_t applied = 0;
+    while (e == hipSuccess && applied < pending_xf_.size()) {
+        e = rt_launch_xform_points(pending_xf_[applied].data(), d_tri9_.as<float>(), npts,
+                                   d_geom_flag_.as<uint32_t>(), stream_);
+        if (e == hipSuccess)
+            applied++;
+    }
+    // (a launch that failed leaves its matrix and the ones behind it queued)
+    pending_xf_.erase(pending_xf_.begin(), pending_xf_.begin() + applied);
+    device_xforms_ += (int64_t)applied;
+    unsigned word = 0;
+    if (e == hipSuccess)
+        e = read_u32(d_geom_flag_.p, stream_, word);
+    if (e != hipSuccess)
+        return hip_fail(e, "object transform on the device");
+    tri9_nonfinite_ = tri9_nonfinite_ || word != 0;
+    return RT_OK;
+}
+
+// tri_ brought up to date for a host reader (the host octree build, brute-force mode, a helper's mirror,
+// the host-path transform, rt_get_triangles): one download after the queued edits, when it is stale
+int Renderer::host_tris()
+{
+    if (!tri_stale_)
+        return RT_OK;
+    int rc = apply_device_edits();
+    if (rc != RT_OK)
+        return rc;
+    hipError_t e = hipSetDevice(device_);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(stream_);
+    if (e == hipSuccess && !tri_.empty())
+        e = hipMemcpy(tri_.data(), d_tri9_.p, tri_.size() * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess)
+        return hip_fail(e, "download (device-transformed triangles)");
+    tri_stale_ = false;
+    return RT_OK;
+}
+
+int Renderer::get_triangles(float* tri9, int64_t* n)
+{
+    if (!n)
+        return fail(RT_EINVAL, "rt_get_triangles: null count");
+    *n = (int64_t)tri_mat_.size();
+    if (!tri9)
+        return RT_OK;
+    int rc = host_tris();
+    if (rc != RT_OK)
+        return rc;
+    if (!tri_.empty())
+        std::memcpy(tri9, tri_.data(), tri_.size() * 4);
+    return RT_OK;
+}
+
 int Renderer::ensure_device_scene()
 {
     hipError_t e = hipSetDevice(device_);
@@ -1073,9 +1163,19 @@ int Renderer::ensure_device_scene()
         auto ms_since = [](clk::time_point t) { return std::chrono::duration<float, std::milli>(clk::now() - t).count(); };
         auto t0 = clk::now();
         int64_t n = (int64_t)tri_mat_.size();
-        for (float c : tri_)
-            if (!std::isfinite(c))
-                return fail(RT_EINVAL, "triangle with a non-finite vertex coordinate");
+        // queued object edits first (frames in flight that read d_tri9_ have ended: sync_slots above)
+        {
+            int rc = apply_device_edits();
+            if (rc != RT_OK)
+                return rc;
+        }
+        // (while tri_ is stale the positions were written by the kernel, which kept the same test's word)
+        bool finite = !tri9_nonfinite_;
+        if (!tri_stale_)
+            for (float c : tri_)
+                finite = finite && std::isfinite(c);
+        if (!finite)
+            return fail(RT_EINVAL, "triangle with a non-finite vertex coordinate");
         bool dev_built = false;
         if (s_.enable_bvh) {
             if (knobs_.gpu_build && n > 0) {
@@ -1083,14 +1183,21 @@ int Renderer::ensure_device_scene()
                 if (rc != RT_OK)
                     return rc;
             }
-            if (!dev_built)
+            if (!dev_built) {
+                int rc = host_tris();
+                if (rc != RT_OK)
+                    return rc;
                 build_flat_octree(tri_.data(), n, s_.bvh_max_depth, s_.bvh_leaf_object_count, oct_);
+            }
             if (oct_.levels > 31)
                 return fail(RT_EUNSUPPORTED, "octree deeper than 31 levels");
             if (!oct_.ordered_slabs)
                 return fail(RT_EINVAL, "octree volume with d_near > d_far");
         } else {
             // brute-force mode (renderer.cpp:1021-1027): triangles in caller order, no nodes
+            int rc = host_tris();
+            if (rc != RT_OK)
+                return rc;
             oct_ = FlatOctree();
             oct_.tris.resize((size_t)n);
             oct_.tri_id.resize((size_t)n);
@@ -1155,7 +1262,6 @@ int Renderer::ensure_device_scene()
             return hip_fail(e, "upload (scene)");
         build_split_ms_[3] = ms_since(t1);
         geom_dirty_ = false;
-        tri9_dirty_ = true;
         build_ms_ = ms_since(t0);
         build_split_ms_[1] = 0.0f;
         wide_tree_ = 0;
@@ -1603,12 +1709,15 @@ int Renderer::launch_raster(const KParams& P, hipStream_t stream)
 {
     hipError_t e;
     const int64_t n = (int64_t)tri_mat_.size();
-    if (tri9_dirty_) {
+    if (!tri9_current_) {   // (else: resident from the device build's staging or a device transform)
+        int rc = host_tris();
+        if (rc != RT_OK)
+            return rc;
         if ((e = d_tri9_.reserve(tri_.size() * 4)) != hipSuccess) return hip_fail(e, "hipMalloc (raster triangles)");
         if (!tri_.empty() &&
             (e = hipMemcpyAsync(d_tri9_.p, tri_.data(), tri_.size() * 4, hipMemcpyHostToDevice, stream)) != hipSuccess)
             return hip_fail(e, "upload (raster triangles)");
-        tri9_dirty_ = false;
+        tri9_current_ = true;
     }
     RasterArgs A;
     std::memset(&A, 0, sizeof(A));

@@ -7,6 +7,7 @@
 
 #include <stdint.h>
 
+#include <array>
 #include <atomic>
 #include <memory>
 #include <mutex>
@@ -97,6 +98,8 @@ struct Knobs {
     int inject_fail = 0;      // RT_INJECT_FRAME_FAIL=k (tests): the k-th ray_trace fails after its image start
     bool gpu_build = false;   // RT_GPU_BUILD=1 / rt_set_device_build: the octree is built on the device
                               // (octree_gpu.hpp; the same bytes as the host build)
+    bool gpu_xform = true;    // RT_GPU_XFORM=0: with the device build on, set_object_transform still transforms
+                              // the host copy and uploads it (else: the resident positions, geom_gpu.hip)
     bool async_accel = true;  // RT_ASYNC_ACCEL=0: the leaf cones / slabs and the wide BVH are built
                               // before the first frame instead of beside it
     bool accel_hold = false;  // RT_ACCEL_HOLD=1 (tests): frames keep the quick wide BVH until rt_finish_accel
@@ -118,6 +121,7 @@ public:
     void set_device_build(bool on) { knobs_.gpu_build = on; }
     int64_t device_builds() const { return device_builds_; }
     int64_t device_wide_builds() const { return device_wide_builds_; }
+    int64_t device_transforms() const { return device_xforms_; }
     // waits for the background build of the leaf cones / slabs and the wide BVH
     int finish_accel();
     bool exact() const { return knobs_.exact; }
@@ -141,6 +145,9 @@ public:
     int set_camera_lens(float fov, float aspect);
     int set_object_transform(const float m[16]);
     int reset_previous_transform();
+    // Renderer::_triangles' positions (renderer.cpp:214-224) as they stand after every transform so far:
+    // *n triangles, [n][9] into tri9 when it is not null (pending device edits are applied first)
+    int get_triangles(float* tri9, int64_t* n);
     int set_texture(int slot, int w, int h, const float* rgba);
     int set_skybox(const int32_t w[6], const int32_t h[6], const float* const faces[6]);
     int reconstruct_bvh_new();
@@ -259,7 +266,7 @@ private:
     void start_accel();
     // release: adopt even under RT_ACCEL_HOLD (rt_finish_accel, and before the geometry is replaced)
     int poll_accel(bool wait, bool release = false);
-    void mirror_from(const Renderer& lead);
+    int mirror_from(Renderer& lead);
     // a multi-device helper (rt_set_devices): the lead builds the octree, the leaf cones / slabs
     // and the wide BVH once; a helper copies the lead's device buffers to its own device
     const Renderer* lead_ = nullptr;
@@ -286,6 +293,28 @@ private:
     WStats wb_dev_stats_;
     int build_wide_device(bool& built);
     int host_wide();
+    // Object edits on the device (geom_gpu.hip).  d_tri9_, the caller-order positions the
+    // device build and the raster path read, is their resident home: tri9_current_ while it holds the
+    // current geometry (after the device build's staging, the raster path's upload or a device
+    // transform; not after set_triangles / clear_geometry, a helper's mirror or a host-path transform).
+    // (A flag, not a geom_ver_: that version also moves with the BVH settings, which leave the
+    // positions alone.)  With the device build on, set_object_transform queues its matrix in
+    // pending_xf_ and leaves tri_ stale; apply_device_edits runs the queue, one launch per matrix in
+    // call order (composed matrices would round differently), and host_tris brings tri_ up to date for
+    // the host readers.  tri_stale_ implies tri9_current_.
+    std::vector<std::array<float, 16>> pending_xf_;
+    bool tri9_current_ = false, tri_stale_ = false;
+    bool tri9_nonfinite_ = false;   // a device transform wrote a non-finite coordinate (until the geometry is replaced)
+    DevBuf d_geom_flag_;            // the kernel's word
+    int64_t device_xforms_ = 0;     // matrices applied by the kernel (rt_get_device_transforms)
+    int apply_device_edits();
+    int host_tris();
+    // tri_ has just been given new contents: d_tri9_ and the queue belong to the geometry before
+    void drop_device_positions()
+    {
+        pending_xf_.clear();
+        tri9_current_ = tri_stale_ = tri9_nonfinite_ = false;
+    }
     struct MultiDev;
     std::unique_ptr<MultiDev> multi_;
     int num_cus_ = 256;
@@ -374,7 +403,6 @@ private:
     // raster path: caller-order triangles, per-triangle piece counts / offsets, the piece
     // table and its texcoords, the z-key buffer, the big-piece list, scan scratch
     DevBuf d_tri9_, d_rcount_, d_roff_, d_pieces_, d_piece_uv_, d_zkey_, d_big_, d_scan_tmp_;
-    bool tri9_dirty_ = true;
     bool want_rgba_ = false, want_hit_ = false, want_shadow_ = false;
     bool aux_valid_ = false;
     // current image (Renderer::_image): internal from the start of ray_trace, downscaled after

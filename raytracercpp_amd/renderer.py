@@ -185,6 +185,22 @@ class Renderer:
     def reset_previous_transform(self):
         self._call("rt_reset_previous_transform")
 
+    def get_triangles(self):
+        """rt_get_triangles: the world-space positions [n, 9] in caller order, after every
+        set_object_transform so far (object edits queued for the device are applied first)."""
+        n = C.c_int64()
+        self._call("rt_get_triangles", None, C.byref(n))
+        tri9 = np.zeros((n.value, 9), np.float32)
+        self._call("rt_get_triangles", ptr(tri9, _f32p), C.byref(n))
+        return tri9
+
+    def device_transforms(self) -> int:
+        """rt_get_device_transforms: object transforms applied by the GPU kernel since the renderer was
+        created (the device build on, RT_GPU_XFORM not 0)."""
+        n = C.c_int64()
+        self._call("rt_get_device_transforms", C.byref(n))
+        return int(n.value)
+
     # -- textures (renderer.h:77-90) ------------------------------------------------
     def _set_tex(self, slot, img):
         if img is None:
