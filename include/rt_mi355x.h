@@ -214,6 +214,48 @@ int rt_get_device_transforms(rt_renderer *r, int64_t *count);
 int rt_transform_points_device(int32_t device, const float m[16], const float *pts, int64_t n, float *out,
                                int32_t *nonfinite, float ms[2]);
 
+/* Geometry from device memory (no reference counterpart; DESIGN.md 5.1 "Geometry input on the device").
+ * rt_set_triangles_device is rt_set_triangles with the positions read from memory of the handle's device:
+ * d_verts is [nv][3] floats and d_idx [n][3] int32 vertex indices, or with d_idx NULL d_verts is the
+ * flat [n][9] (nv == 3 n).  mat ([n]) and uv6 ([n][6] or NULL) are host arrays as in rt_set_triangles;
+ * the same limits on n; n == 0 is rt_set_triangles with n == 0 (no launch, pointers unread).
+ * rt_update_vertices_device gives new positions for the current n triangles and keeps their materials
+ * and texture coordinates: RT_ESTATE without geometry, or when the flat form's nv is not 3 n.
+ * Neither touches the previous object transform (rt_set_object_transform composes as before).
+ * hip_stream is the caller's hipStream_t (NULL: the null stream).  The call copies the positions on the
+ * GPU in stream order (geom_gpu.hip, bit for bit): its kernel waits for the work queued on hip_stream
+ * before the call, and hip_stream waits for the kernel, so the caller may reuse its buffers on
+ * hip_stream as soon as the call returns.  The host does not wait for the GPU.
+ * Both pointers must be device memory of the handle's device (hipPointerGetAttributes): else RT_EINVAL,
+ * with the geometry unchanged.  A non-finite coordinate in a referenced vertex, or an index outside
+ * [0, nv) (that corner becomes (0, 0, 0)), is found by the kernel and reported by the next frames with
+ * RT_EINVAL until the geometry is replaced.  With the device build off the next build downloads the
+ * positions once and builds on the host: the same frames.
+ * rt_get_device_ingests: launches of that kernel since rt_create. */
+int rt_set_triangles_device(rt_renderer *r, const float *d_verts, int64_t nv, const int32_t *d_idx, const int32_t *mat,
+                            const float *uv6, int64_t n, void *hip_stream);
+int rt_update_vertices_device(rt_renderer *r, const float *d_verts, int64_t nv, const int32_t *d_idx, void *hip_stream);
+int rt_get_device_ingests(rt_renderer *r, int64_t *count);
+
+/* The kernel alone on host arrays: uploads verts ([nv][3]) and idx ([n][3], or NULL for the flat form
+ * with nv == 3 n) to 'device', gathers into out_tri9 ([n][9]) and copies it back; *flags bit 0: a
+ * written coordinate is not finite, bit 1: an index outside [0, nv) (zeros written); ms (optional) =
+ * {the kernel by HIP events, the whole call on the host clock}.  RT_EINVAL for a null pointer, a
+ * negative count or a flat form with nv != 3 n; RT_EHIP (rt_last_error) without a usable device;
+ * n == 0: RT_OK, no device touched. */
+int rt_gather_triangles_device(int32_t device, const float *verts, int64_t nv, const int32_t *idx, int64_t n,
+                               float *out_tri9, int32_t *flags, float ms[2]);
+
+/* Deferred refinement.  on != 0: a geometry change builds what the next frame needs (the
+ * octree and the quick wide BVH) and does not start the background build of the leaf cones / slabs, the
+ * SAH wide BVH and the origin cones: frames stay on the quick tree (rt_stats.wide_tree 1; the octree, 0,
+ * with RT_WBVH_QUICK_FIRST=0), the same images.  For geometry that changes every frame, whose
+ * background build would be joined by the next change and dropped.  rt_finish_accel on a geometry not
+ * refined yet starts that build, waits and adopts it; after on == 0 the next frame starts it.
+ * Also RT_ACCEL_DEFER=1 at rt_create.  rt_get_accel_builds: background builds started since rt_create. */
+int rt_set_accel_deferred(rt_renderer *r, int on);
+int rt_get_accel_builds(rt_renderer *r, int64_t *count);
+
 /* Single-process multi-device rendering (no reference counterpart: the reference renders on
  * one host, RenderThread::run, QT/mainWindowThreads.cpp:39-65).  ids[0] must be the handle's
  * device; n = 0 (or ids NULL) returns to one device.  rt_render then renders on every device

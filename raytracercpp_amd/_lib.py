@@ -105,6 +105,12 @@ SIGNATURES = {
     "rt_get_triangles": (C.c_int, [_H, _f32p, _i64p]),
     "rt_get_device_transforms": (C.c_int, [_H, _i64p]),
     "rt_transform_points_device": (C.c_int, [C.c_int32, _f32p, _f32p, C.c_int64, _f32p, _i32p, _f32p]),
+    "rt_set_triangles_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_void_p, _i32p, _f32p, C.c_int64, C.c_void_p]),
+    "rt_update_vertices_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "rt_get_device_ingests": (C.c_int, [_H, _i64p]),
+    "rt_gather_triangles_device": (C.c_int, [C.c_int32, _f32p, C.c_int64, _i32p, C.c_int64, _f32p, _i32p, _f32p]),
+    "rt_set_accel_deferred": (C.c_int, [_H, C.c_int]),
+    "rt_get_accel_builds": (C.c_int, [_H, _i64p]),
     "rt_set_texture": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, _f32p]),
     "rt_set_skybox": (C.c_int, [_H, _i32p, _i32p, C.POINTER(_f32p)]),
     "rt_reconstruct_bvh_new": (C.c_int, [_H]),
@@ -163,7 +169,17 @@ SIGNATURES = {
                                     _i64p]),
 }
 
+# the geometry-input entry points: an older build named by RT_LIB_PATH (development, tools/deform_time.py's
+# row against another commit's library) may lack them; the in-tree library must have every symbol
+GEOMETRY_INPUT = ("rt_set_triangles_device", "rt_update_vertices_device", "rt_get_device_ingests",
+                  "rt_gather_triangles_device", "rt_set_accel_deferred", "rt_get_accel_builds")
+
 _lib = None
+
+
+def has(name):
+    """Whether the loaded library exports ``name`` (see GEOMETRY_INPUT)."""
+    return hasattr(lib(), name)
 
 
 def lib():
@@ -181,6 +197,8 @@ def lib():
             pass
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
+            if name in GEOMETRY_INPUT and os.environ.get("RT_LIB_PATH") and not hasattr(L, name):
+                continue
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -267,6 +285,61 @@ def transform_points_device(m, pts, device=0):
     check(lib().rt_transform_points_device(device, ptr(m, _f32p), ptr(pts, _f32p), pts.shape[0], ptr(out, _f32p),
                                            C.byref(flag), ptr(ms, _f32p)), "rt_transform_points_device")
     return out, int(flag.value), (float(ms[0]), float(ms[1]))
+
+
+def gather_triangles_device(verts, indices=None, device=0):
+    """rt_gather_triangles_device: (tri9 [n, 9], flags, (kernel ms by HIP events, whole call ms)) of the
+    geometry-input kernel alone on host arrays: verts [nv, 3] gathered through indices [n, 3] (int32), or
+    with indices None verts is the flat [n, 9].  flags bit 0: a written coordinate is not finite; bit 1: an
+    index outside [0, nv) (zeros written).  Raises RtError (RT_EHIP: no usable device)."""
+    verts = f32(verts)
+    if indices is None:
+        verts = verts.reshape(-1, 9)
+        n, nv, idx = verts.shape[0], 3 * verts.shape[0], None
+    else:
+        verts = verts.reshape(-1, 3)
+        idx = np.ascontiguousarray(indices, np.int32).reshape(-1, 3)
+        n, nv = idx.shape[0], verts.shape[0]
+    out = np.zeros((n, 9), np.float32)
+    flags = C.c_int32()
+    ms = np.zeros(2, np.float32)
+    check(lib().rt_gather_triangles_device(device, ptr(verts, _f32p), nv, ptr(idx, _i32p), n, ptr(out, _f32p),
+                                           C.byref(flags), ptr(ms, _f32p)), "rt_gather_triangles_device")
+    return out, int(flags.value), (float(ms[0]), float(ms[1]))
+
+
+def device_geometry_args(verts, indices, device):
+    """The checks of Renderer.set_triangles_device / update_vertices_device on their torch tensors:
+    (verts pointer, nv, indices pointer or None, n).  verts: float32 [n, 9] (indices None) or [nv, 3] with
+    indices int32 [n, 3]; both contiguous tensors on the GPU with index ``device``.  TypeError for a
+    non-tensor or a wrong dtype, ValueError for the wrong place, layout or shape."""
+    import torch
+
+    def form(t, name, dtype, cols):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: a torch tensor on the GPU is needed, not {type(t).__name__}")
+        if t.dtype != dtype:
+            raise TypeError(f"{name}: dtype {t.dtype}, {dtype} is needed")
+        if t.dim() != 2 or t.shape[1] != cols:
+            raise ValueError(f"{name}: shape {tuple(t.shape)}, [n, {cols}] is needed")
+
+    def place(t, name):
+        if not t.is_cuda:
+            raise ValueError(f"{name}: the tensor is on {t.device}, not on a GPU")
+        if t.device.index != int(device):
+            raise ValueError(f"{name}: the tensor is on GPU {t.device.index}, the renderer on GPU {int(device)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: the tensor is not contiguous")
+
+    # (what each tensor is before where it lies: the first kind of mistake shows without a GPU)
+    form(verts, "verts", torch.float32, 9 if indices is None else 3)
+    if indices is not None:
+        form(indices, "indices", torch.int32, 3)
+    place(verts, "verts")
+    if indices is None:
+        return verts.data_ptr(), 3 * verts.shape[0], None, verts.shape[0]
+    place(indices, "indices")
+    return verts.data_ptr(), verts.shape[0], indices.data_ptr(), indices.shape[0]
 
 
 def load_obj(path, xform, mat_offset=0):

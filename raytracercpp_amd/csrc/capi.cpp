@@ -970,6 +970,103 @@ int rt_transform_points_device(int32_t device, const float m[16], const float* p
     return RT_OK;
 }
 
+int rt_set_triangles_device(rt_renderer* r, const float* d_verts, int64_t nv, const int32_t* d_idx, const int32_t* mat,
+                            const float* uv6, int64_t n, void* hip_stream)
+{
+    return guarded(R(r), [&] {
+        return R(r)->set_triangles_device(d_verts, nv, d_idx, mat, uv6, n, reinterpret_cast<hipStream_t>(hip_stream));
+    });
+}
+int rt_update_vertices_device(rt_renderer* r, const float* d_verts, int64_t nv, const int32_t* d_idx, void* hip_stream)
+{
+    return guarded(R(r), [&] {
+        return R(r)->update_vertices_device(d_verts, nv, d_idx, reinterpret_cast<hipStream_t>(hip_stream));
+    });
+}
+int rt_get_device_ingests(rt_renderer* r, int64_t* count)
+{
+    return guarded(R(r), [&] {
+        if (!count)
+            return RT_EINVAL;
+        *count = R(r)->device_ingests();
+        return RT_OK;
+    });
+}
+int rt_set_accel_deferred(rt_renderer* r, int on)
+{
+    return guarded(R(r), [&] {
+        R(r)->set_accel_deferred(on != 0);
+        return RT_OK;
+    });
+}
+int rt_get_accel_builds(rt_renderer* r, int64_t* count)
+{
+    return guarded(R(r), [&] {
+        if (!count)
+            return RT_EINVAL;
+        *count = R(r)->accel_builds();
+        return RT_OK;
+    });
+}
+
+int rt_gather_triangles_device(int32_t device, const float* verts, int64_t nv, const int32_t* idx, int64_t n,
+                               float* out_tri9, int32_t* flags, float ms[2])
+{
+    if (n < 0 || nv < 0 || !flags || (n > 0 && (!verts || !out_tri9)) || (!idx && nv != 3 * n))
+        return bad("rt_gather_triangles_device: bad arguments");
+    auto t0 = std::chrono::steady_clock::now();
+    *flags = 0;
+    if (ms)
+        ms[0] = ms[1] = 0.0f;
+    if (n == 0)
+        return RT_OK;
+    auto hip_bad = [](hipError_t e, const char* what) {
+        g_err = std::string("rt_gather_triangles_device: ") + what + ": " + hipGetErrorString(e);
+        return RT_EHIP;
+    };
+    hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess)
+        return hip_bad(e, "hipSetDevice");
+    rt::DevBuf d_verts, d_idx, d_out, d_flag;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    struct EvGuard {
+        hipEvent_t* ev;
+        ~EvGuard()
+        {
+            for (int i = 0; i < 2; i++)
+                if (ev[i]) (void)hipEventDestroy(ev[i]);
+        }
+    } guard{ev};
+    const size_t vbytes = (size_t)nv * 12, ibytes = idx ? (size_t)n * 12 : 0, obytes = (size_t)n * 36;
+    if ((e = d_verts.reserve(vbytes)) != hipSuccess || (e = d_idx.reserve(ibytes)) != hipSuccess ||
+        (e = d_out.reserve(obytes)) != hipSuccess || (e = d_flag.reserve(4)) != hipSuccess ||
+        (e = hipEventCreate(&ev[0])) != hipSuccess || (e = hipEventCreate(&ev[1])) != hipSuccess)
+        return hip_bad(e, "allocation");
+    if ((vbytes && (e = hipMemcpy(d_verts.p, verts, vbytes, hipMemcpyHostToDevice)) != hipSuccess) ||
+        (ibytes && (e = hipMemcpy(d_idx.p, idx, ibytes, hipMemcpyHostToDevice)) != hipSuccess) ||
+        (e = hipMemset(d_flag.p, 0, 4)) != hipSuccess)
+        return hip_bad(e, "upload");
+    if ((e = hipEventRecord(ev[0], nullptr)) != hipSuccess)
+        return hip_bad(e, "hipEventRecord");
+    if ((e = rt_launch_gather_points(d_verts.as<float>(), nv, idx ? d_idx.as<int32_t>() : nullptr, d_out.as<float>(),
+                                     3 * n, d_flag.as<uint32_t>(), nullptr)) != hipSuccess)
+        return hip_bad(e, "launch");
+    float dev_ms = 0.0f;
+    if ((e = hipEventRecord(ev[1], nullptr)) != hipSuccess || (e = hipEventSynchronize(ev[1])) != hipSuccess ||
+        (e = hipEventElapsedTime(&dev_ms, ev[0], ev[1])) != hipSuccess)
+        return hip_bad(e, "kernel");
+    uint32_t word = 0;
+    if ((e = hipMemcpy(out_tri9, d_out.p, obytes, hipMemcpyDeviceToHost)) != hipSuccess ||
+        (e = hipMemcpy(&word, d_flag.p, 4, hipMemcpyDeviceToHost)) != hipSuccess)
+        return hip_bad(e, "readback");
+    *flags = (int32_t)word;
+    if (ms) {
+        ms[0] = dev_ms;
+        ms[1] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return RT_OK;
+}
+
 int rt_wbvh_quick_digest(const float* tri9, int64_t n, int32_t max_depth, int32_t leaf_max_obj_count, uint64_t digest[6],
                          int64_t stats[5], float* ms)
 {

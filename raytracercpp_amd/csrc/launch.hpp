@@ -63,6 +63,11 @@ RT_LAUNCH rt_launch_ocone(const rt::OConeEnt* E, const rt::GTri* tris, const uin
 // geometry edits (geom_gpu.hip): xform_point over pts [n][3] in place; *nonfinite |= 1 when a written
 // coordinate is not finite.  n <= 0: no launch
 RT_LAUNCH rt_launch_xform_points(const float m[16], float* pts, int64_t n, uint32_t* nonfinite, hipStream_t stream);
+// geometry from device memory: tri9 [npts][3] = verts[idx[i]] (idx null: verts[i], npts <= nv), bit for bit;
+// *flags |= 1 when a written coordinate is not finite, |= 2 when an index is outside [0, nv) (zeros
+// written, nothing read).  npts <= 0: no launch
+RT_LAUNCH rt_launch_gather_points(const float* verts, int64_t nv, const int32_t* idx, float* tri9, int64_t npts,
+                                  uint32_t* flags, hipStream_t stream);
 
 // the reflection engine (renderer.cpp drives the levels)
 RT_LAUNCH rt_launch_refl_level0(const rt::KParams* P, rt::FrameRec* fr1, unsigned int* nfr1, hipStream_t stream);

@@ -107,6 +107,7 @@ Knobs Knobs::from_env()
     k.gpu_build = flag("RT_GPU_BUILD", k.gpu_build);
     k.gpu_xform = on("RT_GPU_XFORM", true);
     k.accel_hold = flag("RT_ACCEL_HOLD", k.accel_hold);
+    k.accel_defer = flag("RT_ACCEL_DEFER", k.accel_defer);
     const int chunk = num("RT_REFL_CHUNK_LOG2", k.refl_chunk_log2);
     if (chunk >= 10 && chunk <= 27)   // small values (tests): many chunks per level
         k.refl_chunk_log2 = chunk;
@@ -161,6 +162,8 @@ Renderer::~Renderer()
         if (e) hipEventDestroy(e);
     if (risk_ev_) hipEventDestroy(risk_ev_);
     if (risk_mark_) hipEventDestroy(risk_mark_);
+    for (auto& e : ingest_ev_)
+        if (e) hipEventDestroy(e);
     for (auto& e : ring_)
         if (e) hipEventDestroy(e);
     for (auto& b : band_slot_) {
@@ -249,6 +252,13 @@ int Renderer::set_triangles(const float* tri9, const int32_t* mat, const float* 
         return fail(RT_EUNSUPPORTED, "set_triangles: more than 2^30 triangles");
     tri_.assign(tri9, tri9 + 9 * n);
     drop_device_positions();
+    set_attributes(mat, uv6, n);
+    return RT_OK;
+}
+
+// set_triangles' materials, texture coordinates and flags (the positions are the caller's business)
+void Renderer::set_attributes(const int32_t* mat, const float* uv6, int64_t n)
+{
     tri_mat_.assign(mat, mat + n);
     // the material range, checked by validate() before every launch without re-reading
     // the per-triangle indices (a 1M-triangle scan per frame cost ~0.2 ms of host time)
@@ -263,6 +273,120 @@ int Renderer::set_triangles(const float* tri9, const int32_t* mat, const float* 
     else
         tri_uv_.clear();
     has_bvh_ = s_.enable_bvh;
+    geom_dirty_ = true, ++geom_ver_;
+}
+
+// rt_set_triangles_device / rt_update_vertices_device: both arrays must be device memory of device_.
+// (A pointer the runtime does not know leaves a sticky error behind: cleared.)
+int Renderer::check_device_input(const void* d_verts, const void* d_idx)
+{
+    for (const void* p : {d_verts, d_idx}) {
+        if (!p)
+            continue;
+        hipPointerAttribute_t a{};
+        hipError_t e = hipPointerGetAttributes(&a, p);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(RT_EINVAL, "geometry input: not a device pointer");
+        }
+        if (a.type != hipMemoryTypeDevice)
+            return fail(RT_EINVAL, "geometry input: not device memory");
+        if (a.device != device_)
+            return fail(RT_EINVAL, "geometry input: memory of another device");
+    }
+    return RT_OK;
+}
+
+// d_tri9_ [n][9] from the caller's device arrays, eagerly and in stream order: stream_ waits for the
+// caller's stream, the kernel runs on stream_, the caller's stream waits for the kernel.  The host waits
+// only for frames in flight on other streams that read d_tri9_ (the raster path).  On RT_OK the
+// positions' state is the device input's; the caller sets the rest of the geometry.
+int Renderer::ingest_positions(const float* d_verts, int64_t nv, const int32_t* d_idx, int64_t n, hipStream_t stream)
+{
+    hipError_t e = hipSetDevice(device_);
+    if (e != hipSuccess)
+        return hip_fail(e, "hipSetDevice");
+    int rc = check_device_input(d_verts, d_idx);
+    if (rc != RT_OK)
+        return rc;
+    if (sync_slots() != RT_OK)
+        return RT_EHIP;
+    for (hipEvent_t& ev : ingest_ev_)
+        if (!ev && (e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess)
+            return hip_fail(e, "hipEventCreate (geometry input)");
+    if ((e = d_ingest_flag_.reserve(4)) != hipSuccess)
+        return hip_fail(e, "hipMalloc (geometry input)");
+    // (from here the positions before are gone: growing d_tri9_ drops its contents)
+    pending_xf_.clear();
+    if ((e = d_tri9_.reserve((size_t)n * 36)) == hipSuccess && (e = hipEventRecord(ingest_ev_[0], stream)) == hipSuccess &&
+        (e = hipStreamWaitEvent(stream_, ingest_ev_[0], 0)) == hipSuccess &&
+        (e = hipMemsetAsync(d_ingest_flag_.p, 0, 4, stream_)) == hipSuccess &&
+        (e = rt_launch_gather_points(d_verts, nv, d_idx, d_tri9_.as<float>(), 3 * n, d_ingest_flag_.as<uint32_t>(),
+                                     stream_)) == hipSuccess &&
+        (e = hipEventRecord(ingest_ev_[1], stream_)) == hipSuccess)
+        e = hipStreamWaitEvent(stream, ingest_ev_[1], 0);
+    if (e != hipSuccess) {
+        // (neither the old positions nor the new ones are whole: no triangles)
+        tri_.clear();
+        drop_device_positions();
+        set_attributes(nullptr, nullptr, 0);
+        return hip_fail(e, "geometry input on the device");
+    }
+    ++device_ingests_;
+    tri9_current_ = tri_stale_ = true;
+    tri9_nonfinite_ = tri9_badidx_ = false;
+    ingest_flag_live_ = true;
+    return RT_OK;
+}
+
+// the ingest kernel's word, once per ingest, where the host waits for stream_ anyway
+int Renderer::read_ingest_flag()
+{
+    if (!ingest_flag_live_)
+        return RT_OK;
+    unsigned word = 0;
+    hipError_t e = hipSetDevice(device_);
+    if (e == hipSuccess)
+        e = read_u32(d_ingest_flag_.p, stream_, word);
+    if (e != hipSuccess)
+        return hip_fail(e, "geometry input on the device");
+    ingest_flag_live_ = false;
+    tri9_nonfinite_ = tri9_nonfinite_ || (word & 1u) != 0;
+    tri9_badidx_ = tri9_badidx_ || (word & 2u) != 0;
+    return RT_OK;
+}
+
+int Renderer::set_triangles_device(const float* d_verts, int64_t nv, const int32_t* d_idx, const int32_t* mat,
+                                   const float* uv6, int64_t n, hipStream_t stream)
+{
+    if (n < 0 || nv < 0 || (n > 0 && (!d_verts || !mat)))
+        return fail(RT_EINVAL, "set_triangles_device: null arrays");
+    if (n >= (int64_t)1 << 30)
+        return fail(RT_EUNSUPPORTED, "set_triangles_device: more than 2^30 triangles");
+    if (n == 0)
+        return set_triangles(nullptr, nullptr, nullptr, 0);
+    if (!d_idx && nv != 3 * n)
+        return fail(RT_EINVAL, "set_triangles_device: the flat form needs nv == 3 n");
+    int rc = ingest_positions(d_verts, nv, d_idx, n, stream);
+    if (rc != RT_OK)
+        return rc;
+    // (tri_ is stale and stays as it is: host_tris sizes and fills it when a host reader asks)
+    set_attributes(mat, uv6, n);
+    return RT_OK;
+}
+
+int Renderer::update_vertices_device(const float* d_verts, int64_t nv, const int32_t* d_idx, hipStream_t stream)
+{
+    const int64_t n = (int64_t)tri_mat_.size();
+    if (nv < 0 || !d_verts)
+        return fail(RT_EINVAL, "update_vertices_device: null array");
+    if (n == 0)
+        return fail(RT_ESTATE, "update_vertices_device: no geometry");
+    if (!d_idx && nv != 3 * n)
+        return fail(RT_ESTATE, "update_vertices_device: the flat form needs nv == 3 x the current triangle count");
+    int rc = ingest_positions(d_verts, nv, d_idx, n, stream);
+    if (rc != RT_OK)
+        return rc;
     geom_dirty_ = true, ++geom_ver_;
     return RT_OK;
 }
@@ -427,7 +551,10 @@ int Renderer::set_object_transform(const float m[16])
         std::vector<float> out(tri_.size());
         mat::transform_points(t, tri_.data(), (int64_t)n, out.data());
         tri_.swap(out);
+        // (a device input's bad index left zeros in tri_, which no host scan can tell from the caller's)
+        const bool badidx = tri9_badidx_;
         drop_device_positions();
+        tri9_badidx_ = badidx;
     }
     has_bvh_ = true;
     geom_dirty_ = true, ++geom_ver_;
@@ -640,6 +767,7 @@ int Renderer::reserve_risk(size_t nodes)
 
 void Renderer::start_accel()
 {
+    ++accel_builds_;
     accel_state_.store(1);
     oc_done_.store(false);
     tree_pending_ = true;
@@ -796,6 +924,11 @@ int Renderer::finish_accel()
     hipError_t e = hipSetDevice(device_);
     if (e != hipSuccess)
         return hip_fail(e, "hipSetDevice");
+    // deferred refinement: the resident geometry's build starts here (a helper's is its lead's)
+    if (unrefined_ && !geom_dirty_ && !lead_) {
+        unrefined_ = false;
+        start_accel();
+    }
     return poll_accel(true, true);
 }
 
@@ -1086,7 +1219,7 @@ int Renderer::apply_device_edits()
         return RT_EHIP;
     if ((e = d_geom_flag_.reserve(4)) != hipSuccess)
         return hip_fail(e, "hipMalloc (object transform)");
-    const int64_t npts = (int64_t)(tri_.size() / 3);
+    const int64_t npts = 3 * (int64_t)tri_mat_.size();   // (tri_ may be unsized: a device input)
     e = hipMemsetAsync(d_geom_flag_.p, 0, 4, stream_);
     size_t applied = 0;
     while (e == hipSuccess && applied < pending_xf_.size()) {
@@ -1116,6 +1249,9 @@ int Renderer::host_tris()
     int rc = apply_device_edits();
     if (rc != RT_OK)
         return rc;
+    if ((rc = read_ingest_flag()) != RT_OK)
+        return rc;
+    tri_.resize(9 * tri_mat_.size());   // (a device input leaves tri_ as it was, of any size)
     hipError_t e = hipSetDevice(device_);
     if (e == hipSuccess)
         e = hipStreamSynchronize(stream_);
@@ -1166,16 +1302,20 @@ int Renderer::ensure_device_scene()
         // queued object edits first (frames in flight that read d_tri9_ have ended: sync_slots above)
         {
             int rc = apply_device_edits();
+            if (rc == RT_OK)
+                rc = read_ingest_flag();
             if (rc != RT_OK)
                 return rc;
         }
-        // (while tri_ is stale the positions were written by the kernel, which kept the same test's word)
+        // (while tri_ is stale the positions were written by a kernel, which kept the same test's word)
         bool finite = !tri9_nonfinite_;
         if (!tri_stale_)
             for (float c : tri_)
                 finite = finite && std::isfinite(c);
         if (!finite)
             return fail(RT_EINVAL, "triangle with a non-finite vertex coordinate");
+        if (tri9_badidx_)
+            return fail(RT_EINVAL, "vertex index out of range");
         bool dev_built = false;
         if (s_.enable_bvh) {
             if (knobs_.gpu_build && n > 0) {
@@ -1281,7 +1421,11 @@ int Renderer::ensure_device_scene()
         }
         build_split_ms_[2] = 0.0f;
         // the leaf cones / slabs and the wide BVH: beside the next frames (RT_ASYNC_ACCEL=0: now)
-        if (s_.enable_bvh) {
+        unrefined_ = s_.enable_bvh && knobs_.accel_defer;
+        if (unrefined_) {
+            // deferred refinement: frames stay on what was just built until rt_finish_accel, or the first
+            // frame after the switch is turned off, starts the build below for this geometry
+        } else if (s_.enable_bvh) {
             start_accel();
             if (!knobs_.async_accel) {
                 int rc = poll_accel(true);
@@ -1296,7 +1440,13 @@ int Renderer::ensure_device_scene()
             wb_on_device_ = false;
         }
     } else {
-        int rc = poll_accel(false);
+        bool started = false;
+        if (unrefined_ && !knobs_.accel_defer) {   // (the switch was turned off: this geometry's build, late)
+            unrefined_ = false;
+            start_accel();
+            started = true;
+        }
+        int rc = poll_accel(started && !knobs_.async_accel);
         if (rc != RT_OK)
             return rc;
     }

@@ -104,6 +104,8 @@ struct Knobs {
                               // before the first frame instead of beside it
     bool accel_hold = false;  // RT_ACCEL_HOLD=1 (tests): frames keep the quick wide BVH until rt_finish_accel
                               // adopts the background's SAH tree
+    bool accel_defer = false; // RT_ACCEL_DEFER=1 / rt_set_accel_deferred: a geometry change does not start the
+                              // background build; rt_finish_accel, or the switch turned off, does
     static Knobs from_env();
 };
 
@@ -122,6 +124,15 @@ public:
     int64_t device_builds() const { return device_builds_; }
     int64_t device_wide_builds() const { return device_wide_builds_; }
     int64_t device_transforms() const { return device_xforms_; }
+    int64_t device_ingests() const { return device_ingests_; }
+    int64_t accel_builds() const { return accel_builds_; }
+    // geometry changes build the octree and the quick wide BVH only (rt_set_accel_deferred)
+    void set_accel_deferred(bool on) { knobs_.accel_defer = on; }
+    // set_triangles with the positions taken from memory of device_ (rt_set_triangles_device), and new
+    // positions for the current triangles (rt_update_vertices_device)
+    int set_triangles_device(const float* d_verts, int64_t nv, const int32_t* d_idx, const int32_t* mat,
+                             const float* uv6, int64_t n, hipStream_t stream);
+    int update_vertices_device(const float* d_verts, int64_t nv, const int32_t* d_idx, hipStream_t stream);
     // waits for the background build of the leaf cones / slabs and the wide BVH
     int finish_accel();
     bool exact() const { return knobs_.exact; }
@@ -309,11 +320,28 @@ private:
     int64_t device_xforms_ = 0;     // matrices applied by the kernel (rt_get_device_transforms)
     int apply_device_edits();
     int host_tris();
+    // Geometry input on the device (gather_points_kernel): d_tri9_ written from the caller's
+    // device arrays in stream order, tri_ left stale and unsized (host_tris sizes it from tri_mat_).  The
+    // kernel's word (bit 0 a non-finite coordinate, bit 1 an index out of range) is read by the next
+    // build or host reader (read_ingest_flag) and is sticky until the geometry is replaced.
+    DevBuf d_ingest_flag_;
+    bool ingest_flag_live_ = false;   // the word has not been read since the last ingest
+    bool tri9_badidx_ = false;
+    int64_t device_ingests_ = 0;      // gather launches (rt_get_device_ingests)
+    hipEvent_t ingest_ev_[2] = {nullptr, nullptr};   // the caller's stream -> stream_, and back
+    void set_attributes(const int32_t* mat, const float* uv6, int64_t n);
+    int check_device_input(const void* d_verts, const void* d_idx);
+    int ingest_positions(const float* d_verts, int64_t nv, const int32_t* d_idx, int64_t n, hipStream_t stream);
+    int read_ingest_flag();
+    // Deferred refinement (rt_set_accel_deferred): the resident octree has had no background build started
+    bool unrefined_ = false;
+    int64_t accel_builds_ = 0;        // start_accel calls (rt_get_accel_builds)
     // tri_ has just been given new contents: d_tri9_ and the queue belong to the geometry before
     void drop_device_positions()
     {
         pending_xf_.clear();
         tri9_current_ = tri_stale_ = tri9_nonfinite_ = false;
+        ingest_flag_live_ = tri9_badidx_ = false;
     }
     struct MultiDev;
     std::unique_ptr<MultiDev> multi_;

@@ -124,6 +124,52 @@ class Renderer:
         uv = None if uv6 is None else f32(uv6).reshape(-1, 6)
         self._call("rt_set_triangles", ptr(tri9, _f32p), ptr(mat, _i32p), ptr(uv, _f32p), tri9.shape[0])
 
+    @staticmethod
+    def _stream_ptr(stream, device):
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(device)
+        return C.c_void_p(int(stream.cuda_stream))
+
+    def set_triangles_device(self, verts, mat, uv6=None, indices=None, stream=None):
+        """rt_set_triangles_device: set_triangles with the positions read from GPU memory.  verts: a
+        contiguous float32 torch tensor on this renderer's GPU, [n, 9], or [nv, 3] with indices int32
+        [n, 3]; mat / uv6 host arrays as in set_triangles.  The copy runs in the order of ``stream`` (a
+        torch stream; default the current one): verts and indices may be overwritten on it as soon as
+        the call returns.  A non-finite coordinate or a bad index raises at the next frame."""
+        vp, nv, ip, n = _lib.device_geometry_args(verts, indices, self.device)
+        mat = np.ascontiguousarray(mat, np.int32).reshape(-1)
+        uv = None if uv6 is None else f32(uv6).reshape(-1, 6)
+        if mat.shape[0] != n or (uv is not None and uv.shape[0] != n):
+            raise ValueError(f"set_triangles_device: {n} triangles but {mat.shape[0]} materials"
+                             + ("" if uv is None else f" and {uv.shape[0]} texture coordinates"))
+        self._call("rt_set_triangles_device", C.c_void_p(vp), nv, C.c_void_p(ip), ptr(mat, _i32p), ptr(uv, _f32p), n,
+                   self._stream_ptr(stream, self.device))
+
+    def update_vertices_device(self, verts, indices=None, stream=None):
+        """rt_update_vertices_device: new positions for the current triangles from GPU memory (tensors
+        and stream as in set_triangles_device); materials and texture coordinates stay."""
+        vp, nv, ip, _ = _lib.device_geometry_args(verts, indices, self.device)
+        self._call("rt_update_vertices_device", C.c_void_p(vp), nv, C.c_void_p(ip),
+                   self._stream_ptr(stream, self.device))
+
+    def device_ingests(self) -> int:
+        """rt_get_device_ingests: launches of the geometry-input kernel since the renderer was created."""
+        n = C.c_int64()
+        self._call("rt_get_device_ingests", C.byref(n))
+        return int(n.value)
+
+    def set_accel_deferred(self, on: bool = True):
+        """rt_set_accel_deferred: geometry changes build the octree and the quick wide BVH
+        only; finish_accel, or the first frame after the switch is off, starts the background build."""
+        self._call("rt_set_accel_deferred", 1 if on else 0)
+
+    def accel_builds(self) -> int:
+        """rt_get_accel_builds: background builds started since the renderer was created."""
+        n = C.c_int64()
+        self._call("rt_get_accel_builds", C.byref(n))
+        return int(n.value)
+
     def add_sphere(self, center: Sequence[float], radius: float, mat_index: int = 0):
         self._call("rt_add_sphere", float(center[0]), float(center[1]), float(center[2]), float(radius), int(mat_index))
 
