@@ -450,6 +450,14 @@ int rt_kernel_times(rt_renderer *r, float *ms, int32_t n);
 /* shadow / reflection ray counts of the last rt_render_bands_device (waits for that launch);
  * RT_ESTATE before the first rt_render_bands_device call */
 int rt_band_counters(rt_renderer *r, int64_t *shadow_rays, int64_t *reflection_rays);
+/* the tile mask of the last frame launch (rt_ray_trace / rt_render_bands_device; RT_TILE_MASK=0: none): one bit
+ * per 8 x 8 block of the internal image, block (bx, by) at bit bx & 31 of words[by * info[2] + (bx >> 5)]; a
+ * clear bit: every pixel of the block is the background's and was written without a ray.  src 0: as the
+ * device computed it; 1: recomputed on the host from the same wide-BVH nodes.  info: blocks per row, block
+ * rows, words per row, 1 when the launch used the mask (0: it had none, every bit is set), the entries of the
+ * tree cut it was computed from.  words may be NULL (info only); cap: its size in words.  RT_ESTATE before
+ * the first frame launch */
+int rt_tile_mask(rt_renderer *r, int32_t src, uint32_t *words, int64_t cap, int32_t info[5]);
 
 /* ---- tp2/src/mat.cpp restated (host) ---- */
 /* kind: 0 Translation(x,y,z) 1 RotationX(x deg) 2 RotationY 3 RotationZ 4 Scale(x,y,z) 5 Identity */

@@ -136,6 +136,7 @@ SIGNATURES = {
     "rt_risk_words": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_uint64), C.c_int64, _i64p, _i64p]),
     "rt_kernel_times": (C.c_int, [_H, _f32p, C.c_int32]),
     "rt_band_counters": (C.c_int, [_H, _i64p, _i64p]),
+    "rt_tile_mask": (C.c_int, [_H, C.c_int32, _u32p, C.c_int64, _i32p]),
     "rt_make_transform": (None, [C.c_int32, C.c_float, C.c_float, C.c_float, _f32p]),
     "rt_compose": (None, [_f32p, _f32p, _f32p]),
     "rt_inverse": (None, [_f32p, _f32p]),

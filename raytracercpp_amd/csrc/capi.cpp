@@ -478,6 +478,10 @@ int rt_kernel_times(rt_renderer* r, float* ms, int32_t n)
 {
     return guarded(R(r), [&] { return ms ? R(r)->kernel_times(ms, n) : RT_EINVAL; });
 }
+int rt_tile_mask(rt_renderer* r, int32_t src, uint32_t* words, int64_t cap, int32_t info[5])
+{
+    return guarded(R(r), [&] { return info ? R(r)->tile_mask(src, words, cap, info) : RT_EINVAL; });
+}
 int rt_band_counters(rt_renderer* r, int64_t* shadow_rays, int64_t* reflection_rays)
 {
     return guarded(R(r), [&] {

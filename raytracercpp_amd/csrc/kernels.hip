@@ -2047,6 +2047,41 @@ __device__ __forceinline__ void trace_split_part(const KParams& P, uint2* lv, in
     }
 }
 
+__device__ __forceinline__ void tile_cost_store(const KParams& P, int tile, uint64_t t0, int lane)
+{
+    const uint64_t c = __builtin_amdgcn_s_memtime() - t0;
+    if (lane == 0) {
+        const uint32_t c32 = c > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)c;
+        P.tile_cost[tile] = c32;
+        tile_stats_add(c32, c32);
+    }
+}
+
+// A tile the mask answers (KParams::tile_mask): what trace_pixel's miss path leaves in every output, without
+// the ray, the query or the SSAA shuffles (the box filter of equal values is that value; fused SSAA: every
+// lane holds a pixel, the block's first lane writes).  Out of line: the frame kernel's loop keeps its registers.
+__device__ __noinline__ void fill_masked_tile(const KParams& P, int lr, int px)
+{
+    const c3 bg = background();
+    const uint32_t c = color_to_argb(bg);
+    const size_t o = (size_t)lr * P.rw + px;
+    if (P.argb) P.argb[o] = c;
+    if (P.ds_out) {
+        const int f = 1 << P.ds_shift;
+        if ((px & (f - 1)) == 0 && (lr & (f - 1)) == 0)
+            P.ds_out[(size_t)(lr >> P.ds_shift) * (size_t)(P.rw >> P.ds_shift) + (size_t)(px >> P.ds_shift)] =
+                qrgb((int)((c >> 16) & 0xffu), (int)((c >> 8) & 0xffu), (int)(c & 0xffu));
+    }
+    if (P.rgba) P.rgba[o] = make_float4(bg.r, bg.g, bg.b, 1.0f);
+    if (P.hit_id) P.hit_id[o] = -1;
+    if (P.hit_t) P.hit_t[o] = rec_fresh().t;
+    if (P.shadow) P.shadow[o] = (uint8_t)0;
+#if RT_COUNT
+    if (P.counters && (threadIdx.x & 63) == 0)
+        atomicAdd(&P.counters[28], 1ull);
+#endif
+}
+
 // Renderer::ray_trace (renderer.cpp:1068-1116): one lane per pixel, one wave
 // per 8x8 tile.  Waves are persistent and pull tiles from the sharded device-scope
 // queue (tile_queue_next): shadow-ray-heavy tiles cluster around the object, so
@@ -2115,6 +2150,17 @@ __global__ __launch_bounds__(BLOCK, OCT ? RT_OCC_OCT : PLAIN ? RT_OCC_PLAIN : RT
                 P.tile_cost[tile] = 0u;
             continue;
         }
+        if (PLAIN && !REFL && !OCT && P.tile_mask) {
+            // the tile mask: no ray of a block whose bit is clear enters the cut, so each
+            // is a certified miss; a tile whose lanes' blocks are all clear is the background's
+            const uint32_t mw = ldg(P.tile_mask + (size_t)(py >> 3) * (size_t)P.mask_wpr + (size_t)(px >> 8));
+            if (!__ballot((mw >> ((px >> 3) & 31)) & 1u)) {
+                fill_masked_tile(P, lr, px);
+                if (P.tile_cost)
+                    tile_cost_store(P, tile, tile_t0, lane);
+                continue;
+            }
+        }
         // ray generation, renderer.cpp:1086-1098
         const v3 rd = camera_dir(P, px, py, cam);
         if (PLAIN) PH_MARK(1);
@@ -2130,14 +2176,8 @@ __global__ __launch_bounds__(BLOCK, OCT ? RT_OCC_OCT : PLAIN ? RT_OCC_PLAIN : RT
         if (P.shadow) P.shadow[o] = (uint8_t)(po.found && po.shadowed);
         if (!PLAIN && P.zbuf) write_ssao_buffers(P, o, po.found, cam, rd, po.fin);
         if (PLAIN) PH_MARK(5);
-        if (P.tile_cost) {   // the tile's shader cycles (heavy-first order of the next launch)
-            const uint64_t c = __builtin_amdgcn_s_memtime() - tile_t0;
-            if (lane == 0) {
-                const uint32_t c32 = c > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)c;
-                P.tile_cost[tile] = c32;
-                tile_stats_add(c32, c32);
-            }
-        }
+        if (P.tile_cost)   // the tile's shader cycles (heavy-first order of the next launch)
+            tile_cost_store(P, tile, tile_t0, lane);
     }
     tile_stats_flush(P, lane);
 #if RT_PHASE_TIME
@@ -3885,6 +3925,118 @@ hipError_t rt_launch_risk_box_init(float* B, size_t nentries, hipStream_t stream
     if (nentries > 0)
         hipLaunchKernelGGL(risk_box_init_kernel, dim3((unsigned)((6 * nentries + 255) / 256)), dim3(256), 0, stream, B,
                            nentries);
+    return hipGetLastError();
+}
+
+// The tile mask's cut (wbvh.hpp wbvh_cut_host, the same levels): one block; buf = two lists of W_CUT_MAX entries
+// and the count at buf[2 W_CUT_MAX]; the cut ends in the first list.  budget <= W_CUT_MAX (the launcher)
+__global__ __launch_bounds__(1024) void wide_cut_kernel(const rt::WNode* __restrict__ nodes, int nnodes, int budget,
+                                                        int max_depth, float QS, uint32_t* buf)
+{
+    __shared__ int s_n, s_next, s_grew;
+    uint32_t* cur = buf;
+    uint32_t* nxt = buf + rt::W_CUT_MAX;
+    const int tid = (int)threadIdx.x;
+    if (tid == 0) {
+        int n = 0;
+        for (int j = 0; j < rt::W_WIDTH; j++)
+            if (nodes[0].child[j] != rt::W_EMPTY)
+                cur[n++] = (uint32_t)j;
+        s_n = n;
+    }
+    __syncthreads();
+    for (int depth = 1; depth < max_depth; depth++) {
+        if (tid == 0) {
+            s_next = 0;
+            s_grew = 0;
+        }
+        __syncthreads();
+        const int n = s_n;
+        int total = 0, grew = 0;
+        for (int i = tid; i < n; i += 1024) {
+            uint32_t out[rt::W_WIDTH];
+            const int k = rt::wbvh_cut_expand(nodes, nnodes, cur[i], QS, out);
+            total += k;
+            grew |= !(k == 1 && out[0] == cur[i]);
+        }
+        if (total)
+            atomicAdd(&s_next, total);
+        if (grew)
+            atomicOr(&s_grew, 1);
+        __syncthreads();
+        const bool stop = !s_grew || s_next > budget;   // (the same for every thread)
+        __syncthreads();
+        if (stop)
+            break;
+        if (tid == 0)
+            s_next = 0;
+        __syncthreads();
+        for (int i = tid; i < n; i += 1024) {
+            uint32_t out[rt::W_WIDTH];
+            const int k = rt::wbvh_cut_expand(nodes, nnodes, cur[i], QS, out);
+            const int base = atomicAdd(&s_next, k);
+            for (int q = 0; q < k; q++)
+                nxt[base + q] = out[q];   // base + k <= the first pass's total <= budget
+        }
+        __syncthreads();
+        if (tid == 0)
+            s_n = s_next;
+        uint32_t* t = cur;
+        cur = nxt;
+        nxt = t;
+        __syncthreads();
+    }
+    const int n = s_n;
+    if (cur != buf)
+        for (int i = tid; i < n; i += 1024)
+            buf[i] = cur[i];
+    if (tid == 0)
+        buf[2 * rt::W_CUT_MAX] = (uint32_t)n;
+}
+
+// The mask of one camera (wbvh.hpp wbvh_mask_host): one thread per cut entry; words zeroed by the launcher
+__global__ __launch_bounds__(256) void wide_mask_kernel(const rt::WNode* __restrict__ nodes, int nnodes,
+                                                        const uint32_t* __restrict__ parent, const uint32_t* __restrict__ cut,
+                                                        rt::WMaskCam C, uint32_t* words)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= cut[2 * rt::W_CUT_MAX] || i >= (uint32_t)rt::W_CUT_MAX)
+        return;
+    const uint32_t en = cut[i];
+    if ((int)(en >> 2) >= nnodes)
+        return;
+    rt::WMaskRect R = rt::wbvh_mask_entry(nodes, nnodes, parent, en, C);
+    R.x0 = max(R.x0, 0);
+    R.y0 = max(R.y0, 0);
+    R.x1 = min(R.x1, C.bw - 1);
+    R.y1 = min(R.y1, C.bh - 1);
+    if (R.x0 > R.x1)
+        return;
+    for (int y = R.y0; y <= R.y1; y++)
+        for (int w = R.x0 >> 5; w <= R.x1 >> 5; w++) {
+            uint32_t* p = words + (size_t)y * C.wpr + w;
+            const uint32_t m = rt::wbvh_mask_word(R, w);
+            if ((__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & m) != m)
+                atomicOr(p, m);
+        }
+}
+
+hipError_t rt_launch_wide_cut(const rt::WNode* wnodes, int nnodes, int budget, int max_depth, uint32_t* buf, hipStream_t stream)
+{
+    budget = budget < rt::W_WIDTH ? rt::W_WIDTH : (budget > rt::W_CUT_MAX ? rt::W_CUT_MAX : budget);
+    hipLaunchKernelGGL(wide_cut_kernel, dim3(1), dim3(1024), 0, stream, wnodes, nnodes, budget, max_depth, W_QS_CLOSEST, buf);
+    return hipGetLastError();
+}
+
+hipError_t rt_launch_wide_mask(const rt::WNode* wnodes, int nnodes, const uint32_t* parent, const uint32_t* cut, int budget,
+                               const rt::WMaskCam* C, uint32_t* words, hipStream_t stream)
+{
+    budget = budget < rt::W_WIDTH ? rt::W_WIDTH : (budget > rt::W_CUT_MAX ? rt::W_CUT_MAX : budget);
+    hipError_t e = hipMemsetAsync(words, 0, (size_t)C->bh * C->wpr * 4, stream);
+    if (e != hipSuccess)
+        return e;
+    hipLaunchKernelGGL(wide_mask_kernel, dim3((budget + 255) / 256), dim3(256), 0, stream, wnodes, nnodes, parent, cut,
+                       *C, words);
     return hipGetLastError();
 }
 

@@ -69,6 +69,11 @@ struct KParams {
     // none): a ray from cam_pos whose line misses [sb_lo, sb_hi] is a miss without a node load
     float sb_lo[3], sb_hi[3];
     int32_t sb_valid;
+    // the tile mask (wbvh.hpp wbvh_mask_rect; nullptr: none): one bit per 8 x 8 block of the
+    // whole internal image, block (px >> 3, py >> 3) at bit (px >> 3) & 31 of word (py >> 3) mask_wpr + (px >> 8);
+    // a clear bit: no ray of the block enters the cut through the wide BVH, every pixel is the background's
+    const uint32_t* tile_mask;
+    int32_t mask_wpr;
     // the origin cones (ocone.hpp; cells nullptr: none resident): the rays without risk words whose
     // ocone_skip holds skip case (b) (the reflection queries, ReflFeed)
     OConeView ocone;
@@ -159,6 +164,7 @@ struct KParams {
                                     // tests, [12] uncertified queries, [14] certificate k-DOP tests, [16..21]
                                     // uncertified queries by reason (overflow, NaN, overflowed-only, tie, t
                                     // outside (0, inf), certificate failed), [22..27] wide-BVH loop iterations
+                                    // [28] tiles the tile mask answered
                                     // (all but [0..2]: RT_COUNT builds only); then the tile-queue heads,
                                     // shard s at counters[NCOUNTERS + 16 s]
     unsigned long long* dbg;        // diagnostic builds (RT_PHASE_TIME): per wave [DBG_WAVES][DBG_WORDS], else nullptr

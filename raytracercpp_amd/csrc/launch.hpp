@@ -56,6 +56,12 @@ RT_LAUNCH rt_launch_wide_risk(const rt::GTri* wtris, const uint4* wmeta, const r
                               const rt::WNode* wnodes, const uint32_t* tri_leaf, const uint32_t* parent, uint32_t* K,
                               float* B, unsigned long long* risk, int n, int nnodes, const rt::WRiskArgs* A,
                               uint32_t* cap, const float* cap_dir, hipStream_t stream);
+// the tile mask (wbvh.hpp): the cut of the resident tree into buf (2 W_CUT_MAX + 1 words: the
+// entries, scratch, the count), once per tree; the mask of one camera into words (bh x wpr), zeroed first
+// (parent: WBvh::parent on the device, node -> its parent's entry)
+RT_LAUNCH rt_launch_wide_cut(const rt::WNode* wnodes, int nnodes, int budget, int max_depth, uint32_t* buf, hipStream_t stream);
+RT_LAUNCH rt_launch_wide_mask(const rt::WNode* wnodes, int nnodes, const uint32_t* parent, const uint32_t* cut, int budget,
+                              const rt::WMaskCam* C, uint32_t* words, hipStream_t stream);
 RT_LAUNCH rt_launch_ocone(const rt::OConeEnt* E, const rt::GTri* tris, const uint32_t* todo, int n, const float lo[3],
                           const int32_t dim[3], double h, double r, double slack, double QS, double cos_cap,
                           uint2* cells, size_t ncells, hipStream_t stream);

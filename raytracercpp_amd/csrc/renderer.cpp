@@ -100,6 +100,8 @@ Knobs Knobs::from_env()
     k.refl_sorted_frames = flag("RT_REFL_SORTED_FRAMES", k.refl_sorted_frames);
     k.risk_cap = flag("RT_RISK_CAP", k.risk_cap);
     k.scene_bound = flag("RT_SCENE_BOUND", k.scene_bound);
+    k.tile_mask = flag("RT_TILE_MASK", k.tile_mask);
+    k.cut_budget = std::min((int)W_CUT_MAX, std::max((int)W_WIDTH, num("RT_TILE_MASK_CUT", k.cut_budget)));
     k.ocone = flag("RT_OCONE", k.ocone);
     k.ocone_dim = std::min(1024, std::max(1, num("RT_OCONE_DIM", k.ocone_dim)));
     k.inject_fail = num("RT_INJECT_FRAME_FAIL", 0);   // tests: the k-th ray_trace fails after its image start
@@ -145,6 +147,10 @@ int Renderer::init(std::string& err)
         e = hipEventCreateWithFlags(&risk_ev_, hipEventDisableTiming);
     if (e == hipSuccess)
         e = hipEventCreateWithFlags(&risk_mark_, hipEventDisableTiming);
+    if (e == hipSuccess)
+        e = hipEventCreateWithFlags(&mask_ev_, hipEventDisableTiming);
+    if (e == hipSuccess)
+        e = hipEventCreateWithFlags(&mask_mark_, hipEventDisableTiming);
     if (e != hipSuccess) {
         err = std::string("HIP init failed: ") + hipGetErrorString(e);
         return RT_EHIP;
@@ -162,6 +168,8 @@ Renderer::~Renderer()
         if (e) hipEventDestroy(e);
     if (risk_ev_) hipEventDestroy(risk_ev_);
     if (risk_mark_) hipEventDestroy(risk_mark_);
+    if (mask_ev_) hipEventDestroy(mask_ev_);
+    if (mask_mark_) hipEventDestroy(mask_mark_);
     for (auto& e : ingest_ev_)
         if (e) hipEventDestroy(e);
     for (auto& e : ring_)
@@ -902,6 +910,7 @@ int Renderer::poll_accel(bool wait, bool release)
             return RT_EHIP;
         risk_valid_ = false;
         sb_root_valid_ = false;
+        cut_valid_ = false;
         risk_nodes_ = wn;
         risk_tris_ = wt;
         ++accel_ver_;
@@ -951,6 +960,7 @@ int Renderer::adopt_from_lead()
         poll_accel(true, true);
         cones_ready_ = wide_ready_ = lslab_ready_ = ocone_ready_ = false;
         sb_root_valid_ = false;
+        cut_valid_ = false;
         auto t0 = std::chrono::steady_clock::now();
         oct_ = FlatOctree();   // (never built here)
         oct_nn_ = L.oct_nn_;
@@ -1002,6 +1012,7 @@ int Renderer::adopt_from_lead()
         wide_ready_ = L.wide_ready_;
         risk_valid_ = false;
         sb_root_valid_ = false;
+        cut_valid_ = false;
         risk_nodes_ = L.risk_nodes_;
         risk_tris_ = L.risk_tris_;
         mir_accel_ = L.accel_ver_;
@@ -1295,6 +1306,7 @@ int Renderer::ensure_device_scene()
         poll_accel(true, true);
         cones_ready_ = wide_ready_ = lslab_ready_ = ocone_ready_ = false;
         sb_root_valid_ = false;
+        cut_valid_ = false;
         using clk = std::chrono::steady_clock;
         auto ms_since = [](clk::time_point t) { return std::chrono::duration<float, std::milli>(clk::now() - t).count(); };
         auto t0 = clk::now();
@@ -1415,6 +1427,7 @@ int Renderer::ensure_device_scene()
                 return rc;
             risk_valid_ = false;
             sb_root_valid_ = false;
+            cut_valid_ = false;
             risk_nodes_ = wn;
             risk_tris_ = wt;
             ++accel_ver_;
@@ -2025,7 +2038,7 @@ int Renderer::trace_frame()
     }
     if (wait_slots(stream_) != RT_OK)   // band launches in flight share the engine / raster buffers
         return RT_EHIP;
-    if ((rc = prepare_risk(P, stream_)) != RT_OK)
+    if ((rc = prepare_risk(P, stream_)) != RT_OK || (rc = prepare_mask(P, stream_, mask_main_)) != RT_OK)
         return rc;
     bool zeroed = false;   // heavy_prep_kernel clears the counter words itself
     if ((rc = prepare_heavy(P, tc_main_, stream_, 0, &zeroed)) != RT_OK)
@@ -2531,7 +2544,7 @@ int Renderer::render_bands_impl(int band_rows, int rank, int nranks, const int32
         for (auto& ev : ring_)
             if ((e = hipEventCreate(&ev)) != hipSuccess) return hip_fail(e, "hipEventCreate");
     }
-    if ((rc = prepare_risk(P, stream)) != RT_OK)
+    if ((rc = prepare_risk(P, stream)) != RT_OK || (rc = prepare_mask(P, stream, S.mask)) != RT_OK)
         return rc;
     bool zeroed = false;   // heavy_prep_kernel clears the counter words itself (one dispatch fewer)
     bool overlapped = false;   // another band launch still in flight (frames in flight)
@@ -2655,6 +2668,60 @@ int Renderer::prepare_risk(KParams& P, hipStream_t stream)
         P.risk_cap = reinterpret_cast<const float*>(d_wrisk_.as<uint8_t>() + (size_t)risk_nodes_ * 288);
         std::memcpy(P.cap_dir, risk_cap_dir_, sizeof P.cap_dir);
     }
+    return RT_OK;
+}
+
+// The tile mask (KParams::tile_mask, wbvh.hpp wbvh_mask_rect) of a frame launch.  The cut is
+// computed once per resident tree (the computing stream first waits for the launches in flight, whose mask
+// kernels may read the old one; every other stream's mask kernel waits for it, mask_ev_).  The mask is the
+// launching stream's own (M): recomputed on that stream, ahead of the frame, when the camera's matrices, the
+// render size, the light's finiteness or the cut changed since the stream's last launch -- the stream's
+// earlier launches read the old words before it, and no other stream reads them, so a moving camera keeps
+// its frames in flight.  No mask (nullptr) for anything but the plain kernel over the wide BVH with an
+// affine camera; RT_TILE_MASK=0: none.
+int Renderer::prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M)
+{
+    P.tile_mask = nullptr;
+    P.mask_wpr = 0;
+    mask_last_ = nullptr;
+    mask_seen_ = true;
+    if (!knobs_.tile_mask || !P.wnodes || !P.plain || P.has_reflection || P.zbuf || P.nbuf || risk_nodes_ <= 0 || !d_wlinks_.p ||
+        s_.hybrid_rasterization_tracing)
+        return RT_OK;
+    const WMaskCam C = wbvh_mask_cam(P.proj_inv, P.cam_to_world, P.proj_mode, P.proj_w, P.c2w_affine, P.cam_pos, P.light,
+                                     P.scene_scale, W_QS_CLOSEST, P.rw, P.rh);
+    if (!C.valid)
+        return RT_OK;
+    hipError_t e;
+    if (!cut_valid_) {
+        if (wait_slots(stream) != RT_OK)
+            return RT_EHIP;
+        if ((e = d_cut_.reserve((size_t)(2 * W_CUT_MAX + 1) * 4)) != hipSuccess)
+            return hip_fail(e, "hipMalloc (tile mask cut)");
+        if ((e = rt_launch_wide_cut(P.wnodes, (int)risk_nodes_, knobs_.cut_budget, W_CUT_DEPTH, d_cut_.as<uint32_t>(), stream)) !=
+                hipSuccess ||
+            (e = hipEventRecord(mask_mark_, stream)) != hipSuccess ||
+            (e = hipStreamWaitEvent(fence_stream_, mask_mark_, 0)) != hipSuccess ||
+            (e = hipEventRecord(mask_ev_, fence_stream_)) != hipSuccess)
+            return hip_fail(e, "wide_cut_kernel");
+        mask_ev_live_ = true;
+        cut_valid_ = true;
+        cut_gen_++;
+    }
+    if (M.cut_gen != cut_gen_ || std::memcmp(&C, &M.cam, sizeof C)) {
+        M.cut_gen = 0;
+        if ((e = M.words.reserve((size_t)C.bh * C.wpr * 4)) != hipSuccess)
+            return hip_fail(e, "hipMalloc (tile mask)");
+        if ((mask_ev_live_ && (e = hipStreamWaitEvent(stream, mask_ev_, 0)) != hipSuccess) ||
+            (e = rt_launch_wide_mask(P.wnodes, (int)risk_nodes_, d_wlinks_.as<uint32_t>() + risk_tris_, d_cut_.as<uint32_t>(),
+                                     knobs_.cut_budget, &C, M.words.as<uint32_t>(), stream)) != hipSuccess)
+            return hip_fail(e, "wide_mask_kernel");
+        M.cut_gen = cut_gen_;
+        std::memcpy(&M.cam, &C, sizeof C);
+    }
+    P.tile_mask = M.words.as<uint32_t>();
+    P.mask_wpr = C.wpr;
+    mask_last_ = &M;
     return RT_OK;
 }
 
@@ -3029,6 +3096,63 @@ int Renderer::band_counters(unsigned long long out[2])
     out[0] = cnt[0];
     out[1] = cnt[1];
     take_counters(cnt);
+    return RT_OK;
+}
+
+// The last frame launch's tile mask (rt_tile_mask): src 0 as the device computed it, src 1 recomputed on the
+// host from the resident nodes (read back).  info: blocks per row, block rows, words per row, 1 when the launch
+// was given the mask (0: none; the words are then all-covered), the cut's entries.
+int Renderer::tile_mask(int src, uint32_t* out, int64_t cap, int32_t info[5])
+{
+    hipSetDevice(device_);
+    if (!mask_seen_)
+        return fail(RT_ESTATE, "tile_mask: no frame launch yet");
+    if (src != 0 && src != 1)
+        return fail(RT_EINVAL, "tile_mask: src is 0 (device) or 1 (host)");
+    int rw, rh;
+    render_size(rw, rh);
+    const bool on = mask_last_ != nullptr;
+    const int bw = on ? mask_last_->cam.bw : (rw + 7) / 8, bh = on ? mask_last_->cam.bh : (rh + 7) / 8, wpr = (bw + 31) / 32;
+    info[0] = bw;
+    info[1] = bh;
+    info[2] = wpr;
+    info[3] = on ? 1 : 0;
+    info[4] = 0;
+    const size_t nw = (size_t)bh * wpr;
+    if (!out)
+        return RT_OK;
+    if (cap < (int64_t)nw)
+        return fail(RT_EINVAL, "tile_mask: the buffer is too small");
+    if (!on) {
+        const WMaskRect all = {0, 0, bw - 1, bh - 1};
+        for (int y = 0; y < bh; y++)
+            for (int w = 0; w < wpr; w++)
+                out[(size_t)y * wpr + w] = wbvh_mask_word(all, w);
+        return RT_OK;
+    }
+    hipError_t e = hipDeviceSynchronize();
+    uint32_t ncut = 0;
+    if (e == hipSuccess)
+        e = hipMemcpy(&ncut, d_cut_.as<uint32_t>() + 2 * W_CUT_MAX, 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && src == 0)
+        e = hipMemcpy(out, mask_last_->words.p, nw * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess)
+        return hip_fail(e, "tile_mask");
+    info[4] = (int32_t)ncut;
+    if (src == 1) {
+        std::vector<WNode> nodes((size_t)risk_nodes_);
+        if ((e = hipMemcpy(nodes.data(), d_wnodes_.p, nodes.size() * sizeof(WNode), hipMemcpyDeviceToHost)) != hipSuccess)
+            return hip_fail(e, "download (wide BVH nodes)");
+        std::vector<uint32_t> cut, words, parent(nodes.size());
+        if ((e = hipMemcpy(parent.data(), d_wlinks_.as<uint32_t>() + risk_tris_, parent.size() * 4, hipMemcpyDeviceToHost)) !=
+            hipSuccess)
+            return hip_fail(e, "download (wide BVH parents)");
+        wbvh_cut_host(nodes.data(), (int64_t)nodes.size(), knobs_.cut_budget, W_CUT_DEPTH, W_QS_CLOSEST, cut);
+        wbvh_mask_host(nodes.data(), (int64_t)nodes.size(), parent.data(), cut, mask_last_->cam, words);
+        if (cut.size() != ncut)
+            return fail(RT_ESTATE, "tile_mask: the host's cut differs from the device's in size");
+        std::memcpy(out, words.data(), nw * 4);
+    }
     return RT_OK;
 }
 

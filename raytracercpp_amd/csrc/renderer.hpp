@@ -93,6 +93,9 @@ struct Knobs {
                               // case (b), wbvh.hpp risk_cap_skip)
     bool scene_bound = true;  // RT_SCENE_BOUND=0: no scene bound (camera rays that miss the root's widened frame
                               // still run their root step, wbvh.hpp wbvh_scene_bound)
+    bool tile_mask = true;    // RT_TILE_MASK=0: no tile mask (every background tile generates its rays and runs
+                              // the scene bound, wbvh.hpp wbvh_mask_rect)
+    int cut_budget = W_CUT_BUDGET;  // RT_TILE_MASK_CUT=n (4 .. 65536): the largest cut the mask is computed from
     bool ocone = true;        // RT_OCONE=0: no origin cones (reflection queries always run case (b), ocone.hpp)
     int ocone_dim = 128;      // RT_OCONE_DIM=n: the origin-cone grid's cells along the scene's longest axis
     int inject_fail = 0;      // RT_INJECT_FRAME_FAIL=k (tests): the k-th ray_trace fails after its image start
@@ -200,6 +203,7 @@ public:
     // bracketed by HIP events on the launch stream (synchronises on them)
     int kernel_times(float* ms, int n);
     int band_counters(unsigned long long out[2]);
+    int tile_mask(int src, uint32_t* out, int64_t cap, int32_t info[5]);   // rt_tile_mask
     int debug_read(uint64_t* out, int64_t n);   // diagnostic builds: the per-wave records of the last frame
     int tile_costs(uint32_t* out, int64_t n, int32_t* tiles_x, int32_t* tiles_y);   // trace_frame's last tile costs
     // the resident origin-cone grid (ocone.hpp; rt_ocone_read): its frame, and its words when out holds them
@@ -426,7 +430,24 @@ private:
     // sets P.wrisk (and risk_G / risk_nl) for the frame's camera and light, recomputing the bits on
     // 'stream' when they changed; every launch that reads them waits for their computation
     int prepare_risk(KParams& P, hipStream_t stream);
-    DevBuf d_dbg_;                           // diagnostic per-wave records (RT_DEBUG_WAVES)
+    // the tile mask (wbvh.hpp wbvh_mask_rect): the resident tree's cut (d_cut_: 2 W_CUT_MAX + 1
+    // words; false after every change of tree, as sb_root_valid_; mask_ev_ follows its computation, as
+    // risk_ev_ the risk words') and, per launching stream, the mask of that stream's last camera: a launch
+    // computes its mask on its own stream, so a moving camera does not make the frames in flight wait for
+    // each other.  mask_last_: the mask the last launch was given (nullptr: none).
+    struct MaskSlot {
+        DevBuf words;
+        WMaskCam cam{};        // the camera the words were computed for
+        uint64_t cut_gen = 0;  // and the cut (0: no words yet)
+    };
+    DevBuf d_cut_;
+    bool cut_valid_ = false, mask_ev_live_ = false, mask_seen_ = false;
+    uint64_t cut_gen_ = 0;
+    MaskSlot mask_main_;       // rt_ray_trace's (stream_)
+    MaskSlot* mask_last_ = nullptr;
+    hipEvent_t mask_ev_ = nullptr, mask_mark_ = nullptr;
+    int prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M);
+    DevBuf d_dbg_;                          // diagnostic per-wave records (RT_DEBUG_WAVES)
     bool ssao_ready_ = false;   // the buffers hold the last frame's z / normals
     // raster path: caller-order triangles, per-triangle piece counts / offsets, the piece
     // table and its texcoords, the z-key buffer, the big-piece list, scan scratch
@@ -491,6 +512,7 @@ private:
         std::vector<int32_t> map_host;
         int map_nb = 0;              // global bands of that list's image
         uint64_t used = 0;   // band_uses_ at the slot's last launch (least recently used is recycled)
+        MaskSlot mask;       // the tile mask of the slot's last camera
     };
     static constexpr int BAND_SLOTS = 8;
     BandSlot band_slot_[BAND_SLOTS];

@@ -599,29 +599,72 @@ struct WSceneBound {
     int32_t valid;
 };
 
+// What the bound needs of a node N and the camera, once per (node, camera): N's frame and steps, the query's
+// margin m and its Dn for cam over N's frame (case (a)'s D).  valid = 0: the gates above failed.  Nothing in
+// the bound's derivation is particular to the root: a ray from cam that reaches N enters child j only if its
+// line crosses j's decoded box widened by W_j(N, cam) (wbvh_child_reach).
+struct WBoundCtx {
+    float m, D, smax;
+    float org[3], st[3];
+    int32_t valid;
+};
+
+RT_HD WBoundCtx wbvh_bound_ctx(const WNode& N, const float cam[3], bool light_finite, float S)
+{
+    WBoundCtx C{};
+    const float om = fmaxf(fabsf(cam[0]), fmaxf(fabsf(cam[1]), fabsf(cam[2])));
+    if (!(om < 0x1p26f) || !(S > 0x1p-20f && S < 0x1p20f) || !light_finite)
+        return C;
+    C.m = 0x1p-16f * (om + S);   // kernels.hip wide_margin
+    C.org[0] = N.ox;
+    C.org[1] = N.oy;
+    C.org[2] = N.oz;
+    float f2 = 0.0f;
+    for (int a = 0; a < 3; a++) {
+        C.st[a] = __builtin_bit_cast(float, ((N.exps >> (8 * a)) & 0xffu) << 23);
+        C.smax = fmaxf(C.smax, C.st[a]);
+        const float Da = C.org[a] - cam[a];
+        const float f = fmaxf(fabsf(Da), fabsf(__builtin_fmaf(255.0f, C.st[a], Da)));
+        f2 = a == 0 ? f * f : f2 + f * f;   // (fx fx + fy fy) + fz fz, as the query's Dn
+    }
+    const float Dn = sqrtf(f2) * (1.0f + 0x1p-16f) + C.m;
+    if (!(Dn < 0x1p28f))
+        return C;   // (a NaN or infinite frame as well)
+    C.D = Dn * (1.0f + 0x1p-20f);
+    C.valid = 1;
+    return C;
+}
+
+// W_j(N, cam) before the margin terms (+ 1.125 m, relative 2^-19): the larger of case (a)'s Rlat + Rpar (1 +
+// 2^-16) at qa = QS and case (b)'s 2 rho + step; < 0: child j has no finite reach or rho
+RT_HD double wbvh_child_reach(const WNode& N, int j, const WBoundCtx& C, float QS)
+{
+    const uint32_t e = N.ext[j];
+    if ((e >> 24) == 255u)
+        return -1.0;
+    const float smin = fmaxf(wq_val_nz(e & 0xffu, WQ_UNIT), W_SMIN_FLOOR);
+    const float L = wq_val_nz(e >> 24, WQ_LEN);
+    const WReach wr = wq_reach(QS, smin, L, C.D);
+    float Rlat, Rpar;
+    wq_split(wr, L, C.D, Rlat, Rpar);
+    const float rho = wq_len(N.ext2[j] & 0xffu);
+    if (!(wr.E < INFINITY) || !(Rlat < INFINITY) || !(Rpar < INFINITY) || !(rho < INFINITY))
+        return -1.0;
+    const double rs = fmax(1.0, (double)W_R_SCALE);
+    return fmax(rs * ((double)Rlat + (double)Rpar * (1.0 + 0x1p-16)), 2.0 * (double)rho + (double)C.smax);
+}
+
 inline WSceneBound wbvh_scene_bound(const WNode& root, const float cam[3], const float* light, float S, float QS,
                                     double scale = 1.0)
 {
     WSceneBound B{};
-    const float om = fmaxf(fabsf(cam[0]), fmaxf(fabsf(cam[1]), fabsf(cam[2])));
-    if (!(om < 0x1p26f) || !(S > 0x1p-20f && S < 0x1p20f))
+    const WBoundCtx C = wbvh_bound_ctx(
+        root, cam, !light || (std::isfinite(light[0]) && std::isfinite(light[1]) && std::isfinite(light[2])), S);
+    if (!C.valid)
         return B;
-    if (light && !(std::isfinite(light[0]) && std::isfinite(light[1]) && std::isfinite(light[2])))
-        return B;
-    const float m = 0x1p-16f * (om + S);   // kernels.hip wide_margin
-    const float org[3] = {root.ox, root.oy, root.oz};
-    float st[3], f2 = 0.0f, smax = 0.0f;
-    for (int a = 0; a < 3; a++) {
-        st[a] = __builtin_bit_cast(float, ((root.exps >> (8 * a)) & 0xffu) << 23);
-        smax = fmaxf(smax, st[a]);
-        const float Da = org[a] - cam[a];
-        const float f = fmaxf(fabsf(Da), fabsf(__builtin_fmaf(255.0f, st[a], Da)));
-        f2 = a == 0 ? f * f : f2 + f * f;   // (fx fx + fy fy) + fz fz, as the query's Dn
-    }
-    const float Dn = std::sqrt(f2) * (1.0f + 0x1p-16f) + m;
-    if (!(Dn < 0x1p28f))
-        return B;   // (a NaN or infinite frame as well)
-    const float D = Dn * (1.0f + 0x1p-20f);
+    const float m = C.m;
+    const float* org = C.org;
+    const float* st = C.st;
     double W = 0.0;
     int qlo[3] = {255, 255, 255}, qhi[3] = {0, 0, 0};
     bool any = false;
@@ -629,19 +672,10 @@ inline WSceneBound wbvh_scene_bound(const WNode& root, const float cam[3], const
         if (root.child[j] == W_EMPTY)
             continue;
         any = true;
-        const uint32_t e = root.ext[j];
-        if ((e >> 24) == 255u)
+        const double Wj = wbvh_child_reach(root, j, C, QS);
+        if (Wj < 0.0)
             return B;
-        const float smin = fmaxf(wq_val_nz(e & 0xffu, WQ_UNIT), W_SMIN_FLOOR);
-        const float L = wq_val_nz(e >> 24, WQ_LEN);
-        const WReach wr = wq_reach(QS, smin, L, D);
-        float Rlat, Rpar;
-        wq_split(wr, L, D, Rlat, Rpar);
-        const float rho = wq_len(root.ext2[j] & 0xffu);
-        if (!(wr.E < INFINITY) || !(Rlat < INFINITY) || !(Rpar < INFINITY) || !(rho < INFINITY))
-            return B;
-        const double rs = std::max(1.0, (double)W_R_SCALE);
-        W = std::max(W, std::max(rs * ((double)Rlat + (double)Rpar * (1.0 + 0x1p-16)), 2.0 * (double)rho + (double)smax));
+        W = std::max(W, Wj);
         for (int a = 0; a < 3; a++) {
             qlo[a] = std::min(qlo[a], (int)root.qlo[a][j]);
             qhi[a] = std::max(qhi[a], (int)root.qhi[a][j]);
@@ -687,6 +721,298 @@ RT_HD bool scene_bound_rejects(const float lo[3], const float hi[3], v3 o, v3 d)
     const float tmin = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fminf(z0, z1));
     const float tmax = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fmaxf(z0, z1));
     return tmin > __builtin_fmaf(fabsf(tmax), SL, tmax);
+}
+
+// ---------------------------------------------------------------------------------
+// The tile mask: the scene bound taken a few levels down the tree and applied per 8 x 8
+// block of the image, once per camera.
+//
+// The cut: entries (node << 2 | child slot) such that every root-to-leaf path crosses exactly one.  It
+// starts as the root's non-empty children and is expanded level by level: an entry whose child is an
+// inner node M is replaced by M's non-empty children when each of them has a finite reach and rho by the
+// tree alone (wbvh_cut_child_ok; what the camera adds, Dn's gate and an overflow, is met in
+// wbvh_mask_rect: such an entry covers the whole image).  A level is expanded as a whole, and only while
+// the cut stays within its budget and the depth limit.
+constexpr int W_CUT_MAX = 1 << 16;   // the largest budget (the cut's buffers)
+#ifndef W_CUT_BUDGET
+#define W_CUT_BUDGET 4096
+#endif
+#ifndef W_CUT_DEPTH
+#define W_CUT_DEPTH 12
+#endif
+
+RT_HD bool wbvh_cut_child_ok(const WNode& M, int k, float QS)
+{
+    const uint32_t e = M.ext[k];
+    if ((e >> 24) == 255u || (M.ext2[k] & 0xffu) == 255u)
+        return false;
+    const float smin = fmaxf(wq_val_nz(e & 0xffu, WQ_UNIT), W_SMIN_FLOOR);
+    const WReach wr = wq_reach(QS, smin, wq_val_nz(e >> 24, WQ_LEN), 0.0f);
+    return wr.E < INFINITY;
+}
+
+// The entries that replace 'entry' in the next level: itself (returns 1, out[0] = entry), or the non-empty
+// children of the inner node its child link names (returns their number)
+RT_HD int wbvh_cut_expand(const WNode* nodes, int64_t nnodes, uint32_t entry, float QS, uint32_t out[W_WIDTH])
+{
+    out[0] = entry;
+    const uint32_t c = nodes[entry >> 2].child[entry & 3u];
+    if ((c & W_LEAF) || (int64_t)c >= nnodes || c >= (1u << 30))
+        return 1;   // (a leaf; W_EMPTY has the leaf bit)
+    const WNode& M = nodes[c];
+    int n = 0;
+    uint32_t tmp[W_WIDTH];
+    for (int k = 0; k < W_WIDTH; k++) {
+        if (M.child[k] == W_EMPTY)
+            continue;
+        if (!wbvh_cut_child_ok(M, k, QS))
+            return 1;
+        tmp[n++] = (c << 2) | (uint32_t)k;
+    }
+    if (n == 0)
+        return 1;
+    for (int k = 0; k < n; k++)
+        out[k] = tmp[k];
+    return n;
+}
+
+// The cut on the host (the device's: kernels.hip wide_cut_kernel, the same levels, in any order)
+inline void wbvh_cut_host(const WNode* nodes, int64_t nnodes, int budget, int max_depth, float QS, std::vector<uint32_t>& cut)
+{
+    cut.clear();
+    if (nnodes <= 0)
+        return;
+    budget = std::min(budget, W_CUT_MAX);
+    for (int j = 0; j < W_WIDTH; j++)
+        if (nodes[0].child[j] != W_EMPTY)
+            cut.push_back((uint32_t)j);
+    std::vector<uint32_t> next;
+    for (int depth = 1; depth < max_depth; depth++) {
+        next.clear();
+        bool grew = false;
+        for (uint32_t en : cut) {
+            uint32_t out[W_WIDTH];
+            const int n = wbvh_cut_expand(nodes, nnodes, en, QS, out);
+            grew |= !(n == 1 && out[0] == en);
+            next.insert(next.end(), out, out + n);
+        }
+        if (!grew || (int64_t)next.size() > budget)
+            break;
+        cut.swap(next);
+    }
+}
+
+// The camera as the mask sees it.  With KParams::proj_mode != 0 and c2w_affine the direction of pixel (x,
+// y) before normalisation (kernels.hip camera_dir) is affine in (x, y): dir = M (x, y, 1).  Minv is M's
+// inverse (double), so a point P has (a, b, s) = Minv (P - cam) and lies on the line of pixel (a / s, b /
+// s), for s of either sign (the bound's test is the line's).  guard (pixels) covers the float rounding
+// of camera_dir against the exact map and the mask's own rounding (wbvh_mask_cam).  scale (tests): each
+// cut box shrunk about its centre.
+struct WMaskCam {
+    double Minv[9];
+    double guard, scale;
+    float cam[3];
+    float S, QS;
+    int32_t rw, rh;         // the internal image
+    int32_t bw, bh, wpr;    // 8 x 8 blocks, 32-bit words per block row: block (bx, by) is bit bx & 31 of word by wpr + (bx >> 5)
+    int32_t light_finite;
+    int32_t valid;
+};
+
+// valid = 0 (no mask): a general projection or camera matrix, non-finite values, a singular M, or a camera
+// whose float rounding the one-pixel guard does not cover.  camera_dir's float evaluation (x_world within
+// 3u, each matrix row a sum of four products, the subtraction of cam, the normalisation's division; u =
+// 2^-24) puts component r of the direction within 22u T_r of the exact affine map's, T_r the sum of the
+// absolute terms of row r of both transforms plus |cam_r| (13u for the maps and the subtraction, u for
+// the division, 8u for a direction moved by up to 4 ulps); as a vector E <= 2^-18 max T.  A direction
+// d + e maps to Minv d + Minv e = (x, y, 1) + (da, db, ds) with |da| <= |row a| E ..., so the pixel moves by at
+// most (|da| + rw |ds|) / (1 - |ds|) <= 2 (|da| + rw |ds|) for |ds| <= 1/2.  The guard is one pixel plus four
+// times that bound (the mask's own arithmetic is in double: its rounding is far below); no mask when the
+// bound exceeds one pixel.  guard_override (tests): a guard to use instead, may be negative.
+inline WMaskCam wbvh_mask_cam(const float proj_inv[16], const float c2w[16], int proj_mode, float proj_w, int c2w_affine,
+                              const float cam[3], const float* light, float S, float QS, int rw, int rh,
+                              const double* guard_override = nullptr, double scale = 1.0)
+{
+    WMaskCam C{};
+    C.rw = rw;
+    C.rh = rh;
+    C.bw = (rw + 7) / 8;
+    C.bh = (rh + 7) / 8;
+    C.wpr = (C.bw + 31) / 32;
+    C.S = S;
+    C.QS = QS;
+    C.scale = scale;
+    C.light_finite = !light || (std::isfinite(light[0]) && std::isfinite(light[1]) && std::isfinite(light[2]));
+    if (proj_mode == 0 || !c2w_affine || rw <= 0 || rh <= 0 || rw > (1 << 20) || rh > (1 << 20) || !C.light_finite)
+        return C;
+    const double pw = proj_mode == 1 ? 1.0 : (double)proj_w;
+    const double ax = 2.0 / rw, bx = 1.0 / rw - 1.0, ay = 2.0 / rh, by = 1.0 / rh - 1.0;
+    double M[9], T = 0.0, Tv[3];
+    for (int r = 0; r < 3; r++) {
+        const float* p = proj_inv + 4 * r;
+        Tv[r] = std::fabs(pw) * (std::fabs((double)p[0]) + std::fabs((double)p[1]) + std::fabs((double)p[2]) + std::fabs((double)p[3]));
+    }
+    double vs[3][3];   // view-space direction: column of x, of y, constant
+    for (int r = 0; r < 3; r++) {
+        const float* p = proj_inv + 4 * r;
+        vs[r][0] = pw * (double)p[0] * ax;
+        vs[r][1] = pw * (double)p[1] * ay;
+        vs[r][2] = pw * ((double)p[0] * bx + (double)p[1] * by - (double)p[2] + (double)p[3]);
+    }
+    for (int r = 0; r < 3; r++) {
+        const float* c = c2w + 4 * r;
+        double Tw = std::fabs((double)c[3]) + std::fabs((double)cam[r]);
+        for (int k = 0; k < 3; k++) {
+            Tw += std::fabs((double)c[k]) * Tv[k];
+            M[3 * r + k] = (double)c[0] * vs[0][k] + (double)c[1] * vs[1][k] + (double)c[2] * vs[2][k];
+        }
+        M[3 * r + 2] += (double)c[3] - (double)cam[r];
+        T = std::max(T, Tw);
+        C.cam[r] = cam[r];
+    }
+    const double c00 = M[4] * M[8] - M[5] * M[7], c01 = M[5] * M[6] - M[3] * M[8], c02 = M[3] * M[7] - M[4] * M[6];
+    const double det = M[0] * c00 + M[1] * c01 + M[2] * c02;
+    if (!std::isfinite(det) || !std::isfinite(T) || det == 0.0)
+        return C;
+    const double id = 1.0 / det;
+    C.Minv[0] = c00 * id;
+    C.Minv[1] = (M[2] * M[7] - M[1] * M[8]) * id;
+    C.Minv[2] = (M[1] * M[5] - M[2] * M[4]) * id;
+    C.Minv[3] = c01 * id;
+    C.Minv[4] = (M[0] * M[8] - M[2] * M[6]) * id;
+    C.Minv[5] = (M[2] * M[3] - M[0] * M[5]) * id;
+    C.Minv[6] = c02 * id;
+    C.Minv[7] = (M[1] * M[6] - M[0] * M[7]) * id;
+    C.Minv[8] = (M[0] * M[4] - M[1] * M[3]) * id;
+    double rn[3], res = 0.0;
+    for (int r = 0; r < 3; r++) {
+        rn[r] = std::sqrt(C.Minv[3 * r] * C.Minv[3 * r] + C.Minv[3 * r + 1] * C.Minv[3 * r + 1] + C.Minv[3 * r + 2] * C.Minv[3 * r + 2]);
+        // (the inverse checked against M: a badly conditioned M has no mask)
+        for (int k = 0; k < 3; k++) {
+            const double x = C.Minv[3 * r] * M[k] + C.Minv[3 * r + 1] * M[3 + k] + C.Minv[3 * r + 2] * M[6 + k];
+            res = std::max(res, std::fabs(x - (r == k ? 1.0 : 0.0)));
+        }
+    }
+    const double E = 0x1p-18 * T;
+    const double ds = rn[2] * E;
+    const double shift = 2.0 * (std::max(rn[0], rn[1]) * E + std::max(rw, rh) * ds);
+    if (!(res < 1e-9) || !(ds <= 0.5) || !(shift <= 1.0))
+        return C;
+    C.guard = guard_override ? *guard_override : 1.0 + 4.0 * shift;
+    C.valid = 1;
+    return C;
+}
+
+// The blocks a cut entry may touch: [x0, x1] x [y0, y1] inclusive (empty: x0 > x1); an entry whose widened
+// box has no projection (a corner on either side of, or near, the camera's plane s = 0; no finite W; a
+// failed gate) covers every block.
+struct WMaskRect {
+    int32_t x0, y0, x1, y1;
+};
+
+RT_HD WMaskRect wbvh_mask_rect(const WNode& N, int j, const WMaskCam& C)
+{
+    const WMaskRect all = {0, 0, C.bw - 1, C.bh - 1};
+    const WBoundCtx B = wbvh_bound_ctx(N, C.cam, C.light_finite != 0, C.S);
+    if (!B.valid)
+        return all;
+    double W = wbvh_child_reach(N, j, B, C.QS);
+    if (W < 0.0)
+        return all;
+    W = (W + 1.125 * (double)B.m) * (1.0 + 0x1p-19);
+    double lo[3], hi[3];
+    for (int a = 0; a < 3; a++) {
+        const double l = (double)B.org[a] + (double)N.qlo[a][j] * (double)B.st[a] - W;
+        const double h = (double)B.org[a] + (double)N.qhi[a][j] * (double)B.st[a] + W;
+        const double c = 0.5 * (l + h), r = 0.5 * (h - l) * C.scale;
+        lo[a] = c - r - (double)C.cam[a];
+        hi[a] = c + r - (double)C.cam[a];
+        if (!(fabs(lo[a]) < 0x1p27) || !(fabs(hi[a]) < 0x1p27) || !(lo[a] <= hi[a]))
+            return all;
+    }
+    double xmin = INFINITY, xmax = -INFINITY, ymin = INFINITY, ymax = -INFINITY, smin = INFINITY, smax = -INFINITY;
+    for (int c = 0; c < 8; c++) {
+        const double px = (c & 1) ? hi[0] : lo[0], py = (c & 2) ? hi[1] : lo[1], pz = (c & 4) ? hi[2] : lo[2];
+        const double a = C.Minv[0] * px + C.Minv[1] * py + C.Minv[2] * pz;
+        const double b = C.Minv[3] * px + C.Minv[4] * py + C.Minv[5] * pz;
+        const double s = C.Minv[6] * px + C.Minv[7] * py + C.Minv[8] * pz;
+        smin = fmin(smin, s);
+        smax = fmax(smax, s);
+        const double x = a / s, y = b / s;
+        xmin = fmin(xmin, x);
+        xmax = fmax(xmax, x);
+        ymin = fmin(ymin, y);
+        ymax = fmax(ymax, y);
+    }
+    // every s of one sign and clear of zero (s is linear: it then keeps that sign over the whole box, whose
+    // projection is the convex hull of the corners')
+    const double sa = fmax(fabs(smin), fabs(smax));
+    if (!(smin * smax > 0.0) || !(fmin(fabs(smin), fabs(smax)) > 0x1p-20 * sa) || !(sa < INFINITY))
+        return all;
+    xmin -= C.guard;
+    xmax += C.guard;
+    ymin -= C.guard;
+    ymax += C.guard;
+    if (!(xmin <= xmax) || !(ymin <= ymax))
+        return WMaskRect{1, 1, 0, 0};   // (a negative guard, tests; NaN cannot occur: every s is clear of zero)
+    if (xmax < 0.0 || ymax < 0.0 || xmin > (double)(C.rw - 1) || ymin > (double)(C.rh - 1))
+        return WMaskRect{1, 1, 0, 0};
+    WMaskRect R;
+    R.x0 = (int32_t)floor(fmax(xmin, 0.0)) >> 3;
+    R.y0 = (int32_t)floor(fmax(ymin, 0.0)) >> 3;
+    R.x1 = (int32_t)ceil(fmin(xmax, (double)(C.rw - 1))) >> 3;
+    R.y1 = (int32_t)ceil(fmin(ymax, (double)(C.rh - 1))) >> 3;
+    return R;
+}
+
+// A cut entry's blocks: a ray that reaches the entry's node N has entered N at its parent, and the parent at
+// its own, so its pixel lies in every ancestor entry's rectangle as well: the intersection along the chain
+// (parent: WBvh::parent, node -> its parent's entry, W_EMPTY for the root; nullptr: the entry's own
+// rectangle).  A deep child's W may exceed its ancestors' (its rho is that of the octree leaves it shares
+// with its siblings), so the chain is what makes a finer cut never worse than a coarser one.
+RT_HD WMaskRect wbvh_mask_entry(const WNode* nodes, int64_t nnodes, const uint32_t* parent, uint32_t entry, const WMaskCam& C)
+{
+    WMaskRect R = wbvh_mask_rect(nodes[entry >> 2], (int)(entry & 3u), C);
+    uint32_t n = entry >> 2;
+    for (int up = 0; parent && up < 64 && R.x0 <= R.x1 && R.y0 <= R.y1; up++) {
+        const uint32_t p = parent[n];
+        if (p == W_EMPTY || (int64_t)(p >> 2) >= nnodes)
+            break;
+        const WMaskRect Q = wbvh_mask_rect(nodes[p >> 2], (int)(p & 3u), C);
+        R.x0 = R.x0 > Q.x0 ? R.x0 : Q.x0;
+        R.y0 = R.y0 > Q.y0 ? R.y0 : Q.y0;
+        R.x1 = R.x1 < Q.x1 ? R.x1 : Q.x1;
+        R.y1 = R.y1 < Q.y1 ? R.y1 : Q.y1;
+        n = p >> 2;
+    }
+    if (R.x0 > R.x1 || R.y0 > R.y1)
+        return WMaskRect{1, 1, 0, 0};
+    return R;
+}
+
+// The bits of rect R in word w of a block row (wbvh_mask_rect's layout)
+RT_HD uint32_t wbvh_mask_word(const WMaskRect& R, int w)
+{
+    const int b0 = R.x0 - 32 * w, b1 = R.x1 - 32 * w;
+    if (b1 < 0 || b0 > 31)
+        return 0u;
+    const uint32_t lo = b0 <= 0 ? 0xFFFFFFFFu : 0xFFFFFFFFu << b0;
+    const uint32_t hi = b1 >= 31 ? 0xFFFFFFFFu : 0xFFFFFFFFu >> (31 - b1);
+    return lo & hi;
+}
+
+// The mask on the host (the device's: kernels.hip wide_mask_kernel): words[bh wpr], a set bit = the block
+// may hold a ray that enters the cut
+inline void wbvh_mask_host(const WNode* nodes, int64_t nnodes, const uint32_t* parent, const std::vector<uint32_t>& cut,
+                           const WMaskCam& C, std::vector<uint32_t>& words)
+{
+    words.assign((size_t)C.bh * C.wpr, 0u);
+    for (uint32_t en : cut) {
+        const WMaskRect R = wbvh_mask_entry(nodes, nnodes, parent, en, C);
+        for (int y = R.y0; y <= R.y1 && R.x0 <= R.x1; y++)
+            for (int w = R.x0 >> 5; w <= R.x1 >> 5; w++)
+                words[(size_t)y * C.wpr + w] |= wbvh_mask_word(R, w);
+    }
 }
 
 // A frame's two risk points (kernels.hip wide_risk_kernel): sel 0 the camera (rays start at it), sel

@@ -471,6 +471,18 @@ class Renderer:
         self._call("rt_band_counters", C.byref(a), C.byref(b))
         return a.value, b.value
 
+    def tile_mask(self, src=0):
+        """The last frame launch's tile mask (rt_tile_mask) -> (covered [block rows, blocks per row] bool, dict):
+        covered[by, bx] False: the 8 x 8 block was written as background without a ray.  src 0: the device's
+        mask, 1: the host's recomputation.  dict: 'on' (False: the launch had no mask), 'cut' entries."""
+        info = np.zeros(5, np.int32)
+        self._call("rt_tile_mask", int(src), None, 0, ptr(info, _i32p))
+        bw, bh, wpr = int(info[0]), int(info[1]), int(info[2])
+        words = np.zeros(bh * wpr, np.uint32)
+        self._call("rt_tile_mask", int(src), ptr(words, _u32p), words.size, ptr(info, _i32p))
+        bits = (words.reshape(bh, wpr)[:, :, None] >> np.arange(32, dtype=np.uint32)) & 1
+        return bits.reshape(bh, wpr * 32)[:, :bw].astype(bool), {"on": bool(info[3]), "cut": int(info[4])}
+
     # -- convenience ----------------------------------------------------------------
     def load_scene(self, sc: SceneData, st: RenderSettings):
         """Settings, camera, light, materials, geometry and textures of a SceneData."""

@@ -45,6 +45,16 @@ def gpu(name, frames, out):
     print("  cycles per tile: " + "  ".join(f"q{q:g} {v[min(v.size - 1, int(q * v.size))]:.0f}" for q in qs))
     print(f"  sum {v.sum():.4g} cycles; the costliest tile = {v[-1] / med:.1f} x median, "
           f"{v[-1] / (v.sum() / 3072):.2f} x the mean cycles per wave (3072 waves)")
+    print("  low quantiles: " + "  ".join(f"q{q:g} {v[int(q * v.size)]:.0f}" for q in (0.01, 0.1, 0.25)) +
+          f"; tiles <= 2 x median: {(v <= 2 * med).sum()} ({(v <= 2 * med).mean() * 100:.1f}%), "
+          f"{v[v <= 2 * med].sum() / v.sum() * 100:.1f}% of the cycles")
+    if hasattr(r, "tile_mask"):   # (the tile mask, DESIGN.md 5.12: a tile of the plain frame is one block)
+        try:
+            cov, info = r.tile_mask(0)
+            print(f"  tile mask: on {info['on']}, cut {info['cut']} entries, {int((~cov).sum())} of {cov.size} tiles masked; "
+                  f"their cycles {c[:cov.shape[0], :cov.shape[1]][~cov].sum():.4g}")
+        except Exception as e:   # (a library without rt_tile_mask)
+            print(f"  tile mask: none ({e})")
     mean = v.mean()
     thr = max(4 * mean, v[-1] / 8)
     print(f"  heavy list threshold {thr:.0f}: {(v >= thr).sum()} tiles, {v[v >= thr].sum() / v.sum() * 100:.1f}% of the cycles")
