@@ -49,6 +49,32 @@ hipError_t DevBuf::reserve(size_t n)
     return hipSuccess;
 }
 
+hipError_t WideDev::reserve(int64_t nodes, int64_t tris)
+{
+    nn = nodes;
+    nt = tris;
+    const size_t n = (size_t)nn, t = (size_t)nt;
+    hipError_t e;
+    if ((e = b_nodes.reserve(n * sizeof(WNode))) != hipSuccess || (e = b_tris.reserve(t * sizeof(GTri))) != hipSuccess ||
+        (e = b_meta.reserve(t * 16)) != hipSuccess || (e = b_tmp.reserve(wide_tmp_bytes(n, t))) != hipSuccess)
+        return e;
+    return b_links.reserve(wide_links_bytes(n, t));
+}
+
+void WideDev::swap(WideDev& o)
+{
+    DevBuf* mine[5] = {&b_nodes, &b_tris, &b_meta, &b_tmp, &b_links};
+    DevBuf* theirs[5] = {&o.b_nodes, &o.b_tris, &o.b_meta, &o.b_tmp, &o.b_links};
+    for (int i = 0; i < 5; i++) mine[i]->swap(*theirs[i]);
+    std::swap(nn, o.nn);
+    std::swap(nt, o.nt);
+}
+
+static float ms_since(std::chrono::steady_clock::time_point t)
+{
+    return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t).count();
+}
+
 // each switch is on unless its variable is set to 0 (RT_DEBUG_WAVES: on when set)
 Knobs Knobs::from_env()
 {
@@ -144,13 +170,9 @@ int Renderer::init(std::string& err)
     for (int i = 0; i < 4 && e == hipSuccess; i++)
         e = hipEventCreate(&ev_[i]);
     if (e == hipSuccess)
-        e = hipEventCreateWithFlags(&risk_ev_, hipEventDisableTiming);
+        e = risk_fence_.create();
     if (e == hipSuccess)
-        e = hipEventCreateWithFlags(&risk_mark_, hipEventDisableTiming);
-    if (e == hipSuccess)
-        e = hipEventCreateWithFlags(&mask_ev_, hipEventDisableTiming);
-    if (e == hipSuccess)
-        e = hipEventCreateWithFlags(&mask_mark_, hipEventDisableTiming);
+        e = cut_fence_.create();
     if (e != hipSuccess) {
         err = std::string("HIP init failed: ") + hipGetErrorString(e);
         return RT_EHIP;
@@ -166,18 +188,14 @@ Renderer::~Renderer()
     if (accel_stream_) hipStreamDestroy(accel_stream_);
     for (auto& e : ev_)
         if (e) hipEventDestroy(e);
-    if (risk_ev_) hipEventDestroy(risk_ev_);
-    if (risk_mark_) hipEventDestroy(risk_mark_);
-    if (mask_ev_) hipEventDestroy(mask_ev_);
-    if (mask_mark_) hipEventDestroy(mask_mark_);
+    risk_fence_.destroy();
+    cut_fence_.destroy();
     for (auto& e : ingest_ev_)
         if (e) hipEventDestroy(e);
     for (auto& e : ring_)
         if (e) hipEventDestroy(e);
-    for (auto& b : band_slot_) {
-        if (b.done) hipEventDestroy(b.done);
-        if (b.mark) hipEventDestroy(b.mark);
-    }
+    for (auto& b : band_slot_)
+        b.fence.destroy();
     if (fence_stream_) hipStreamDestroy(fence_stream_);
     if (stream_) hipStreamDestroy(stream_);
     for (hipEvent_t ev : display_ev_)
@@ -733,8 +751,7 @@ static void leaf_cones(const FlatOctree& o, std::vector<float>& out, std::vector
 // The leaf cones / slabs and the wide BVH of the current octree, on accel_thread_ (DESIGN.md
 // 5.8).  Reads oct_ and the uploaded triangle tables; writes only cones_, lslab_, lsin_, wb_, their
 // device buffers and accel_ms_, none of which a frame reads before poll_accel adopts them.
-hipError_t Renderer::upload_wide(const WBvh& w, DevBuf& nodes, DevBuf& tris, DevBuf& meta, DevBuf& tmp, DevBuf& links,
-                                 hipStream_t stream)
+hipError_t Renderer::upload_wide(const WBvh& w, WideDev& d, hipStream_t stream)
 {
     // the nodes, and the permutation from which the device gathers the wide BVH's triangle records
     // and, per triangle, everything a certified hit needs in one 16-B load: the octree slot (the
@@ -742,35 +759,53 @@ hipError_t Renderer::upload_wide(const WBvh& w, DevBuf& nodes, DevBuf& tris, Dev
     // (kernels.hip wide_gather_kernel)
     hipError_t e;
     hipSetDevice(device_);
-    const size_t nk = w.slot.size(), wn = w.nodes.size() * sizeof(WNode);
-    const size_t nl = w.tri_leaf.size() + w.parent.size();
-    if ((e = nodes.reserve(wn)) != hipSuccess || (e = tris.reserve(nk * sizeof(GTri))) != hipSuccess ||
-        (e = meta.reserve(nk * 16)) != hipSuccess || (e = tmp.reserve(nk * 8)) != hipSuccess ||
-        (e = links.reserve(nl * 4)) != hipSuccess)
+    const size_t nn = w.nodes.size(), nt = w.slot.size();   // (one slot, one tri_leaf per record; one parent per node)
+    if ((e = d.reserve((int64_t)nn, (int64_t)nt)) != hipSuccess)
         return e;
-    int32_t* d_slot = tmp.as<int32_t>();
-    uint32_t* d_leaf = reinterpret_cast<uint32_t*>(d_slot + nk);
-    if ((e = hipMemcpyAsync(links.p, w.tri_leaf.data(), w.tri_leaf.size() * 4, hipMemcpyHostToDevice, stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(links.as<uint32_t>() + w.tri_leaf.size(), w.parent.data(), w.parent.size() * 4,
-                            hipMemcpyHostToDevice, stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(nodes.p, w.nodes.data(), wn, hipMemcpyHostToDevice, stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(d_slot, w.slot.data(), nk * 4, hipMemcpyHostToDevice, stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(d_leaf, w.leaf_of_slot.data(), nk * 4, hipMemcpyHostToDevice, stream)) != hipSuccess)
+    if ((e = hipMemcpyAsync(d.tri_leaf(), w.tri_leaf.data(), nt * 4, hipMemcpyHostToDevice, stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(d.parent(), w.parent.data(), nn * 4, hipMemcpyHostToDevice, stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(d.nodes(), w.nodes.data(), nn * sizeof(WNode), hipMemcpyHostToDevice, stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(d.slot(), w.slot.data(), nt * 4, hipMemcpyHostToDevice, stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(d.leaf_of_slot(), w.leaf_of_slot.data(), nt * 4, hipMemcpyHostToDevice, stream)) != hipSuccess)
         return e;
-    return rt_launch_wide_gather(d_tris_.as<GTri>(), d_slot, d_leaf, d_tri_id_.as<int32_t>(), d_tri_mat_.as<int32_t>(),
-                                 (int)nk, tris.as<GTri>(), meta.as<uint4>(), stream);
+    return rt_launch_wide_gather(d_tris_.as<GTri>(), d.slot(), d.leaf_of_slot(), d_tri_id_.as<int32_t>(),
+                                 d_tri_mat_.as<int32_t>(), (int)nt, d.tris(), d.meta(), stream);
 }
 
-// The risk words' buffer for the resident tree (8 x 8 B words, 8 x 4 B keys and 8 x 24 B boxes per
-// node); growing it replaces the buffer, so launches in flight that read it are waited for first.
+// The risk buffer for a tree of this many nodes; growing it replaces the buffer, so launches in flight that
+// read it are waited for first.
 int Renderer::reserve_risk(size_t nodes)
 {
-    if (d_wrisk_.bytes >= nodes * 288 + 64)
+    if (d_wrisk_.bytes >= wide_risk_bytes(nodes))
         return RT_OK;
     if (d_wrisk_.p && (sync_slots() != RT_OK || hipStreamSynchronize(stream_) != hipSuccess))
         return RT_EHIP;
-    hipError_t e = d_wrisk_.reserve(nodes * 288 + 64);   // (+ the risk caps)
+    hipError_t e = d_wrisk_.reserve(wide_risk_bytes(nodes));
     return e == hipSuccess ? RT_OK : hip_fail(e, "hipMalloc (risk words)");
+}
+
+int Renderer::install_wide(int tree)
+{
+    wide_ready_ = wide_.nn > 0;
+    wide_tree_ = wide_ready_ ? tree : 0;
+    if (wide_ready_) {
+        int rc = reserve_risk((size_t)wide_.nn);
+        if (rc != RT_OK)
+            return rc;
+    }
+    risk_valid_ = false;
+    sb_root_valid_ = false;
+    cut_valid_ = false;
+    ++accel_ver_;
+    return RT_OK;
+}
+
+void Renderer::drop_accel()
+{
+    cones_ready_ = wide_ready_ = lslab_ready_ = ocone_ready_ = false;
+    sb_root_valid_ = false;
+    cut_valid_ = false;
+    wide_.clear();   // (every reader of the counts is gated by wide_ready_: fill_params' P.wnodes)
 }
 
 void Renderer::start_accel()
@@ -788,9 +823,9 @@ void Renderer::start_accel()
             S = std::max(S, std::max(std::fabs(oct_root_.dn[c]), std::fabs(oct_root_.df[c])));
     accel_thread_ = std::thread([this, want_oc, S] {
         using clk = std::chrono::steady_clock;
-        auto ms_since = [](clk::time_point t) { return std::chrono::duration<float, std::milli>(clk::now() - t).count(); };
         hipError_t e = hipSetDevice(device_);
         auto t0 = clk::now();
+        wide_next_.clear();   // (it may hold the tree the last adoption swapped out)
         leaf_cones(oct_, cones_, lslab_, lsin_);
         if (e == hipSuccess && !lslab_.empty()) {
             if ((e = d_lslab_.reserve(lslab_.size() * 4)) == hipSuccess)
@@ -810,7 +845,7 @@ void Renderer::start_accel()
         auto t2 = clk::now();
         hipSetDevice(device_);
         if (e == hipSuccess && !wb_next_.nodes.empty())
-            e = upload_wide(wb_next_, d_wnodes2_, d_wtris2_, d_wmeta2_, d_wtmp2_, d_wlinks2_, accel_stream_);
+            e = upload_wide(wb_next_, wide_next_, accel_stream_);
         if (e == hipSuccess)
             e = hipStreamSynchronize(accel_stream_);
         accel_ms_[2] = ms_since(t2);
@@ -823,7 +858,7 @@ void Renderer::start_accel()
         // triangle.  The host plans, the device searches (ocone_kernel).
         OConeGrid g;
         WBvh w;
-        const GTri* wtris = d_wtris2_.as<GTri>();
+        const GTri* wtris = wide_next_.tris();
         if (e == hipSuccess && want_oc && !wb_next_.nodes.empty()) {
             w.nodes = wb_next_.nodes;
             w.tris = wb_next_.tris;
@@ -895,25 +930,11 @@ int Renderer::poll_accel(bool wait, bool release)
             std::swap(wb_, wb_next_);
             wb_next_ = WBvh();
             wb_on_device_ = false;
-            d_wnodes_.swap(d_wnodes2_);
-            d_wtris_.swap(d_wtris2_);
-            d_wmeta_.swap(d_wmeta2_);
-            d_wtmp_.swap(d_wtmp2_);
-            d_wlinks_.swap(d_wlinks2_);
+            wide_.swap(wide_next_);
         }
-        // (a device-built quick tree that stays resident keeps its counts: wb_ is not its host copy)
-        const int64_t wn = wb_on_device_ ? risk_nodes_ : (int64_t)wb_.nodes.size();
-        const int64_t wt = wb_on_device_ ? risk_tris_ : (int64_t)wb_.tri_leaf.size();
-        wide_ready_ = wn > 0;
-        wide_tree_ = wide_ready_ ? 2 : 0;
-        if (wide_ready_ && reserve_risk((size_t)wn) != RT_OK)
+        // (otherwise the resident quick tree, if any, stays and counts as this geometry's final tree)
+        if (install_wide(2) != RT_OK)
             return RT_EHIP;
-        risk_valid_ = false;
-        sb_root_valid_ = false;
-        cut_valid_ = false;
-        risk_nodes_ = wn;
-        risk_tris_ = wt;
-        ++accel_ver_;
         build_split_ms_[1] = accel_ms_[0];
         build_split_ms_[2] = accel_ms_[1] + accel_ms_[2];
     }
@@ -958,9 +979,7 @@ int Renderer::adopt_from_lead()
     };
     if (geom_dirty_) {
         poll_accel(true, true);
-        cones_ready_ = wide_ready_ = lslab_ready_ = ocone_ready_ = false;
-        sb_root_valid_ = false;
-        cut_valid_ = false;
+        drop_accel();
         auto t0 = std::chrono::steady_clock::now();
         oct_ = FlatOctree();   // (never built here)
         oct_nn_ = L.oct_nn_;
@@ -980,7 +999,7 @@ int Renderer::adopt_from_lead()
             return hip_fail(e, "rt_set_devices: scene copy from the lead device");
         geom_dirty_ = false;
         mir_accel_ = ~0ull;
-        build_ms_ = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        build_ms_ = ms_since(t0);
         build_split_ms_[0] = build_split_ms_[1] = build_split_ms_[2] = 0.0f;
         build_split_ms_[3] = build_ms_;
     }
@@ -993,15 +1012,20 @@ int Renderer::adopt_from_lead()
                 copy(d_lsin_, L.d_lsin_, ns * 4);
             }
         }
+        wide_.clear();
         if (L.wide_ready_) {
-            // (the lead's counts: its tree may be device-built, with no host copy)
-            const size_t wn = (size_t)L.risk_nodes_, wt = (size_t)L.risk_tris_;
-            copy(d_wnodes_, L.d_wnodes_, wn * sizeof(WNode));
-            copy(d_wtris_, L.d_wtris_, wt * sizeof(GTri));
-            copy(d_wmeta_, L.d_wmeta_, wt * 16);
-            copy(d_wlinks_, L.d_wlinks_, (wt + wn) * 4);
+            // what frames and the risk walk read (a helper gathers nothing: the slot maps stay behind)
+            const size_t wn = (size_t)L.wide_.nn, wt = (size_t)L.wide_.nt;
+            wide_.nn = L.wide_.nn;
+            wide_.nt = L.wide_.nt;
+            copy(wide_.b_nodes, L.wide_.b_nodes, wn * sizeof(WNode));
+            copy(wide_.b_tris, L.wide_.b_tris, wt * sizeof(GTri));
+            copy(wide_.b_meta, L.wide_.b_meta, wt * 16);
+            copy(wide_.b_links, L.wide_.b_links, wide_links_bytes(wn, wt));
+            // (a helper sizes the risk buffer without reserve_risk's wait for the frames in flight:
+            // install_wide's call then finds it large enough)
             if (e == hipSuccess)
-                e = d_wrisk_.reserve(wn * 288 + 64);
+                e = d_wrisk_.reserve(wide_risk_bytes((size_t)wide_.nn));
         }
         if (e == hipSuccess)
             e = hipStreamSynchronize(stream_);
@@ -1009,12 +1033,9 @@ int Renderer::adopt_from_lead()
             return hip_fail(e, "rt_set_devices: acceleration structures from the lead device");
         cones_ready_ = L.cones_ready_;
         lslab_ready_ = L.cones_ready_ && L.lslab_ready_;
-        wide_ready_ = L.wide_ready_;
-        risk_valid_ = false;
-        sb_root_valid_ = false;
-        cut_valid_ = false;
-        risk_nodes_ = L.risk_nodes_;
-        risk_tris_ = L.risk_tris_;
+        int rc = install_wide(L.wide_tree_);
+        if (rc != RT_OK)
+            return rc;
         mir_accel_ = L.accel_ver_;
     }
     return RT_OK;
@@ -1144,7 +1165,7 @@ int Renderer::build_octree_device(int64_t n, bool& built)
 }
 
 // The quick wide BVH by the device builder, from the octree build_octree_device left in d_nodes_ /
-// d_tris_: the nodes, the slot maps (d_wtmp_) and the links in place, then the records' gather.  built
+// d_tris_: the nodes, the slot maps and the links of wide_ in place, then the records' gather.  built
 // stays false when the builder does not take the input or a HIP call fails before the tables are used
 // (the caller then builds on the host from the read-back octree: the same tree).
 int Renderer::build_wide_device(bool& built)
@@ -1157,20 +1178,20 @@ int Renderer::build_wide_device(bool& built)
         wq_gpu_ = std::make_unique<WQuickGpuScratch>();
     hipError_t e = hipSuccess;
     int64_t st[5] = {};
-    int rc = build_wbvh_quick_device(*wq_gpu_, d_nodes_.as<GNode>(), d_tris_.as<GTri>(), *oct_dev_info_, d_wnodes_,
-                                     d_wtmp_, d_wlinks_, st, stream_, &e);
+    int rc = build_wbvh_quick_device(*wq_gpu_, d_nodes_.as<GNode>(), d_tris_.as<GTri>(), *oct_dev_info_, wide_.b_nodes,
+                                     wide_.b_tmp, wide_.b_links, st, stream_, &e);
     if (rc == OCT_GPU_OK && st[0] > 0) {
-        const size_t nk = (size_t)st[2];
-        if ((e = d_wtris_.reserve(nk * sizeof(GTri))) == hipSuccess && (e = d_wmeta_.reserve(nk * 16)) == hipSuccess)
-            e = rt_launch_wide_gather(d_tris_.as<GTri>(), d_wtmp_.as<int32_t>(), d_wtmp_.as<uint32_t>() + nk,
-                                      d_tri_id_.as<int32_t>(), d_tri_mat_.as<int32_t>(), (int)nk, d_wtris_.as<GTri>(),
-                                      d_wmeta_.as<uint4>(), stream_);
+        // (the builder sized and wrote the nodes, the slot maps and the links: the records' buffers remain)
+        if ((e = wide_.reserve(st[0], st[2])) == hipSuccess)
+            e = rt_launch_wide_gather(d_tris_.as<GTri>(), wide_.slot(), wide_.leaf_of_slot(), d_tri_id_.as<int32_t>(),
+                                      d_tri_mat_.as<int32_t>(), (int)wide_.nt, wide_.tris(), wide_.meta(), stream_);
         if (e != hipSuccess)
             rc = OCT_GPU_HIP;
     }
     if (rc == OCT_GPU_HIP) {
         // (a sticky error fails the host path's upload just after; any other is left behind)
         (void)hipGetLastError();
+        wide_.clear();
         return RT_OK;
     }
     if (rc != OCT_GPU_OK || st[0] <= 0)
@@ -1192,7 +1213,7 @@ int Renderer::host_wide()
     if (!wb_on_device_ || !wb_.nodes.empty())
         return RT_OK;
     hipError_t e = hipSetDevice(device_);
-    const size_t np = (size_t)risk_nodes_, nt = (size_t)risk_tris_;
+    const size_t np = (size_t)wide_.nn, nt = (size_t)wide_.nt;
     WBvh w;
     w.nodes.resize(np);
     w.slot.resize(nt);
@@ -1201,11 +1222,11 @@ int Renderer::host_wide()
     w.parent.resize(np);
     if (e == hipSuccess)
         e = hipStreamSynchronize(stream_);
-    if (e == hipSuccess) e = hipMemcpy(w.nodes.data(), d_wnodes_.p, np * sizeof(WNode), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(w.slot.data(), d_wtmp_.p, nt * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(w.leaf_of_slot.data(), d_wtmp_.as<char>() + nt * 4, nt * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(w.tri_leaf.data(), d_wlinks_.p, nt * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(w.parent.data(), d_wlinks_.as<char>() + nt * 4, np * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(w.nodes.data(), wide_.nodes(), np * sizeof(WNode), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(w.slot.data(), wide_.slot(), nt * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(w.leaf_of_slot.data(), wide_.leaf_of_slot(), nt * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(w.tri_leaf.data(), wide_.tri_leaf(), nt * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(w.parent.data(), wide_.parent(), np * 4, hipMemcpyDeviceToHost);
     if (e != hipSuccess)
         return hip_fail(e, "download (device-built quick wide BVH)");
     w.leaf_of_k.resize(nt);
@@ -1297,193 +1318,210 @@ int Renderer::ensure_device_scene()
     // frames still in flight on other streams read the buffers replaced below
     if ((geom_dirty_ || mats_dirty_ || tex_dirty_) && sync_slots() != RT_OK)
         return RT_EHIP;
-    if (lead_) {
-        int rc = adopt_from_lead();
-        if (rc != RT_OK)
-            return rc;
-    } else if (geom_dirty_) {
-        // a build of the previous geometry reads oct_: let it finish (its result is dropped)
-        poll_accel(true, true);
-        cones_ready_ = wide_ready_ = lslab_ready_ = ocone_ready_ = false;
-        sb_root_valid_ = false;
-        cut_valid_ = false;
-        using clk = std::chrono::steady_clock;
-        auto ms_since = [](clk::time_point t) { return std::chrono::duration<float, std::milli>(clk::now() - t).count(); };
-        auto t0 = clk::now();
-        int64_t n = (int64_t)tri_mat_.size();
-        // queued object edits first (frames in flight that read d_tri9_ have ended: sync_slots above)
-        {
-            int rc = apply_device_edits();
-            if (rc == RT_OK)
-                rc = read_ingest_flag();
-            if (rc != RT_OK)
-                return rc;
-        }
-        // (while tri_ is stale the positions were written by a kernel, which kept the same test's word)
-        bool finite = !tri9_nonfinite_;
-        if (!tri_stale_)
-            for (float c : tri_)
-                finite = finite && std::isfinite(c);
-        if (!finite)
-            return fail(RT_EINVAL, "triangle with a non-finite vertex coordinate");
-        if (tri9_badidx_)
-            return fail(RT_EINVAL, "vertex index out of range");
-        bool dev_built = false;
-        if (s_.enable_bvh) {
-            if (knobs_.gpu_build && n > 0) {
-                int rc = build_octree_device(n, dev_built);
-                if (rc != RT_OK)
-                    return rc;
-            }
-            if (!dev_built) {
-                int rc = host_tris();
-                if (rc != RT_OK)
-                    return rc;
-                build_flat_octree(tri_.data(), n, s_.bvh_max_depth, s_.bvh_leaf_object_count, oct_);
-            }
-            if (oct_.levels > 31)
-                return fail(RT_EUNSUPPORTED, "octree deeper than 31 levels");
-            if (!oct_.ordered_slabs)
-                return fail(RT_EINVAL, "octree volume with d_near > d_far");
-        } else {
-            // brute-force mode (renderer.cpp:1021-1027): triangles in caller order, no nodes
-            int rc = host_tris();
-            if (rc != RT_OK)
-                return rc;
-            oct_ = FlatOctree();
-            oct_.tris.resize((size_t)n);
-            oct_.tri_id.resize((size_t)n);
-            for (int64_t i = 0; i < n; i++) {
-                const float* p = tri_.data() + 9 * i;
-                v3 a = mk(p[0], p[1], p[2]), b = mk(p[3], p[4], p[5]), c = mk(p[6], p[7], p[8]);
-                v3 ab = b - a, ac = c - a, nn = cross(b - a, c - a);
-                GTri& g = oct_.tris[(size_t)i];
-                g.a[0] = a.x; g.a[1] = a.y; g.a[2] = a.z;
-                g.ab[0] = ab.x; g.ab[1] = ab.y; g.ab[2] = ab.z;
-                g.ac[0] = ac.x; g.ac[1] = ac.y; g.ac[2] = ac.z;
-                g.n[0] = nn.x; g.n[1] = nn.y; g.n[2] = nn.z;
-                oct_.tri_id[(size_t)i] = (int32_t)i;
-            }
-        }
-        build_split_ms_[0] = ms_since(t0);   // (a device build: with its readback)
-        ++(dev_built ? device_builds_ : host_builds_);
-        oct_nn_ = (int64_t)oct_.nodes.size();
-        oct_nt_ = (int64_t)oct_.tris.size();
-        oct_levels_ = oct_.levels;
-        oct_root_ = oct_nn_ > 0 ? oct_.nodes[0] : GNode{};
-        oct_stats_ = oct_.stats;
-        has_uv_dev_ = !tri_uv_.empty();
-        // the octree and the triangle tables (everything the exact path reads), synchronously
-        auto t1 = clk::now();
-        size_t nb = oct_.nodes.size() * sizeof(GNode), tb = oct_.tris.size() * sizeof(GTri);
-        if ((e = d_nodes_.reserve(nb)) != hipSuccess || (e = d_tris_.reserve(tb)) != hipSuccess ||
-            (e = d_tri_id_.reserve(oct_.tri_id.size() * 4)) != hipSuccess ||
-            (e = d_tri_mat_.reserve(tri_mat_.size() * 4)) != hipSuccess ||
-            (e = d_tri_uv_.reserve(tri_uv_.size() * 4)) != hipSuccess)
-            return hip_fail(e, "hipMalloc (scene)");
-        hipSetDevice(device_);
-        // (a device build wrote the three octree tables in place)
-        if (nb && !dev_built) e = hipMemcpyAsync(d_nodes_.p, oct_.nodes.data(), nb, hipMemcpyHostToDevice, stream_);
-        if (e == hipSuccess && tb && !dev_built)
-            e = hipMemcpyAsync(d_tris_.p, oct_.tris.data(), tb, hipMemcpyHostToDevice, stream_);
-        if (e == hipSuccess && !oct_.tri_id.empty() && !dev_built)
-            e = hipMemcpyAsync(d_tri_id_.p, oct_.tri_id.data(), oct_.tri_id.size() * 4, hipMemcpyHostToDevice, stream_);
-        if (e == hipSuccess && !tri_mat_.empty())
-            e = hipMemcpyAsync(d_tri_mat_.p, tri_mat_.data(), tri_mat_.size() * 4, hipMemcpyHostToDevice, stream_);
-        if (e == hipSuccess && !tri_uv_.empty())
-            e = hipMemcpyAsync(d_tri_uv_.p, tri_uv_.data(), tri_uv_.size() * 4, hipMemcpyHostToDevice, stream_);
-        // the quick wide BVH (the octree's own hierarchy, O(n): wbvh.hpp build_wbvh_quick) while the octree
-        // uploads, resident for the next frames until the SAH tree replaces it
-        const bool quick = e == hipSuccess && s_.enable_bvh && knobs_.quick_wbvh && knobs_.wbvh && !knobs_.exact &&
-                           oct_nn_ > 0;
-        wb_ = WBvh();
-        wb_on_device_ = false;
-        if (quick && dev_built) {   // (the octree is in HBM: the quick tree is built from it where it lies)
-            int rc = build_wide_device(wb_on_device_);
-            if (rc != RT_OK)
-                return rc;
-        }
-        if (quick && !wb_on_device_) {   // (its time counts in build_ms, the blocking part; build_split_ms[2] is the SAH tree's)
-            build_wbvh_quick(oct_, wb_, false);   // (records gathered on the device)
-            if (!wb_.nodes.empty())
-                e = upload_wide(wb_, d_wnodes_, d_wtris_, d_wmeta_, d_wtmp_, d_wlinks_, stream_);
-        }
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(stream_);
-        if (e != hipSuccess)
-            return hip_fail(e, "upload (scene)");
-        build_split_ms_[3] = ms_since(t1);
-        geom_dirty_ = false;
-        build_ms_ = ms_since(t0);
-        build_split_ms_[1] = 0.0f;
-        wide_tree_ = 0;
-        const int64_t wn = wb_on_device_ ? wb_dev_stats_.nodes : (int64_t)wb_.nodes.size();
-        const int64_t wt = wb_on_device_ ? wb_dev_stats_.tris : (int64_t)wb_.tri_leaf.size();
-        if (wn > 0) {
-            wide_ready_ = true;
-            wide_tree_ = 1;
-            int rc = reserve_risk((size_t)wn);
-            if (rc != RT_OK)
-                return rc;
-            risk_valid_ = false;
-            sb_root_valid_ = false;
-            cut_valid_ = false;
-            risk_nodes_ = wn;
-            risk_tris_ = wt;
-            ++accel_ver_;
-        }
-        build_split_ms_[2] = 0.0f;
-        // the leaf cones / slabs and the wide BVH: beside the next frames (RT_ASYNC_ACCEL=0: now)
-        unrefined_ = s_.enable_bvh && knobs_.accel_defer;
-        if (unrefined_) {
-            // deferred refinement: frames stay on what was just built until rt_finish_accel, or the first
-            // frame after the switch is turned off, starts the build below for this geometry
-        } else if (s_.enable_bvh) {
-            start_accel();
-            if (!knobs_.async_accel) {
-                int rc = poll_accel(true);
-                if (rc != RT_OK)
-                    return rc;
-            }
-        } else {
-            cones_.clear();
-            lslab_.clear();
-            lsin_.clear();
-            wb_ = WBvh();
-            wb_on_device_ = false;
-        }
-    } else {
+    int rc = RT_OK;
+    if (lead_)
+        rc = adopt_from_lead();
+    else if (geom_dirty_)
+        rc = rebuild_geometry();
+    else {
         bool started = false;
         if (unrefined_ && !knobs_.accel_defer) {   // (the switch was turned off: this geometry's build, late)
             unrefined_ = false;
             start_accel();
             started = true;
         }
-        int rc = poll_accel(started && !knobs_.async_accel);
+        rc = poll_accel(started && !knobs_.async_accel);
+    }
+    if (rc == RT_OK && mats_dirty_)
+        rc = upload_materials();
+    if (rc == RT_OK && tex_dirty_)
+        rc = upload_textures();
+    return rc;
+}
+
+// A geometry change on the lead: the octree and everything the exact path reads, synchronously, with the
+// quick wide BVH; the refinement (start_accel) beside the next frames.
+int Renderer::rebuild_geometry()
+{
+    // a build of the previous geometry reads oct_: let it finish (its result is dropped)
+    poll_accel(true, true);
+    drop_accel();
+    auto t0 = std::chrono::steady_clock::now();
+    const int64_t n = (int64_t)tri_mat_.size();
+    // queued object edits first (frames in flight that read d_tri9_ have ended: ensure_device_scene's sync_slots)
+    int rc = apply_device_edits();
+    if (rc == RT_OK)
+        rc = read_ingest_flag();
+    if (rc != RT_OK)
+        return rc;
+    // (while tri_ is stale the positions were written by a kernel, which kept the same test's word)
+    bool finite = !tri9_nonfinite_;
+    if (!tri_stale_)
+        for (float c : tri_)
+            finite = finite && std::isfinite(c);
+    if (!finite)
+        return fail(RT_EINVAL, "triangle with a non-finite vertex coordinate");
+    if (tri9_badidx_)
+        return fail(RT_EINVAL, "vertex index out of range");
+    bool dev_built = false;
+    if ((rc = build_octree(n, dev_built)) != RT_OK)
+        return rc;
+    build_split_ms_[0] = ms_since(t0);   // (a device build: with its readback)
+    ++(dev_built ? device_builds_ : host_builds_);
+    oct_nn_ = (int64_t)oct_.nodes.size();
+    oct_nt_ = (int64_t)oct_.tris.size();
+    oct_levels_ = oct_.levels;
+    oct_root_ = oct_nn_ > 0 ? oct_.nodes[0] : GNode{};
+    oct_stats_ = oct_.stats;
+    has_uv_dev_ = !tri_uv_.empty();
+    // the uploads are enqueued (e: the first failure among them) and waited for once, below
+    auto t1 = std::chrono::steady_clock::now();
+    hipError_t e = hipSuccess;
+    if ((rc = upload_octree_tables(dev_built, e)) != RT_OK || (rc = build_quick_wide(dev_built, e)) != RT_OK)
+        return rc;
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(stream_);
+    if (e != hipSuccess)
+        return hip_fail(e, "upload (scene)");
+    build_split_ms_[3] = ms_since(t1);
+    geom_dirty_ = false;
+    build_ms_ = ms_since(t0);
+    build_split_ms_[1] = 0.0f;
+    wide_tree_ = 0;
+    if (wide_.nn > 0 && (rc = install_wide(1)) != RT_OK)
+        return rc;
+    build_split_ms_[2] = 0.0f;
+    // the leaf cones / slabs and the wide BVH: beside the next frames (RT_ASYNC_ACCEL=0: now)
+    unrefined_ = s_.enable_bvh && knobs_.accel_defer;
+    if (unrefined_) {
+        // deferred refinement: frames stay on what was just built until rt_finish_accel, or the first
+        // frame after the switch is turned off, starts the build for this geometry
+    } else if (s_.enable_bvh) {
+        start_accel();
+        if (!knobs_.async_accel)
+            return poll_accel(true);
+    } else {
+        cones_.clear();
+        lslab_.clear();
+        lsin_.clear();
+        wb_ = WBvh();
+        wb_on_device_ = false;
+    }
+    return RT_OK;
+}
+
+// The octree of the n current triangles into oct_: by the device builder (dev_built: d_nodes_ / d_tris_ /
+// d_tri_id_ written in place too) or on the host; without a BVH, the brute-force tables.
+int Renderer::build_octree(int64_t n, bool& dev_built)
+{
+    if (s_.enable_bvh) {
+        if (knobs_.gpu_build && n > 0) {
+            int rc = build_octree_device(n, dev_built);
+            if (rc != RT_OK)
+                return rc;
+        }
+        if (!dev_built) {
+            int rc = host_tris();
+            if (rc != RT_OK)
+                return rc;
+            build_flat_octree(tri_.data(), n, s_.bvh_max_depth, s_.bvh_leaf_object_count, oct_);
+        }
+        if (oct_.levels > 31)
+            return fail(RT_EUNSUPPORTED, "octree deeper than 31 levels");
+        if (!oct_.ordered_slabs)
+            return fail(RT_EINVAL, "octree volume with d_near > d_far");
+        return RT_OK;
+    }
+    // brute-force mode (renderer.cpp:1021-1027): triangles in caller order, no nodes
+    int rc = host_tris();
+    if (rc != RT_OK)
+        return rc;
+    oct_ = FlatOctree();
+    oct_.tris.resize((size_t)n);
+    oct_.tri_id.resize((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        const float* p = tri_.data() + 9 * i;
+        v3 a = mk(p[0], p[1], p[2]), b = mk(p[3], p[4], p[5]), c = mk(p[6], p[7], p[8]);
+        v3 ab = b - a, ac = c - a, nn = cross(b - a, c - a);
+        GTri& g = oct_.tris[(size_t)i];
+        g.a[0] = a.x; g.a[1] = a.y; g.a[2] = a.z;
+        g.ab[0] = ab.x; g.ab[1] = ab.y; g.ab[2] = ab.z;
+        g.ac[0] = ac.x; g.ac[1] = ac.y; g.ac[2] = ac.z;
+        g.n[0] = nn.x; g.n[1] = nn.y; g.n[2] = nn.z;
+        oct_.tri_id[(size_t)i] = (int32_t)i;
+    }
+    return RT_OK;
+}
+
+// The octree and the triangle tables (everything the exact path reads) enqueued on stream_; e: the copies'
+// first failure.  (A device build wrote the three octree tables in place.)
+int Renderer::upload_octree_tables(bool dev_built, hipError_t& e)
+{
+    size_t nb = oct_.nodes.size() * sizeof(GNode), tb = oct_.tris.size() * sizeof(GTri);
+    if ((e = d_nodes_.reserve(nb)) != hipSuccess || (e = d_tris_.reserve(tb)) != hipSuccess ||
+        (e = d_tri_id_.reserve(oct_.tri_id.size() * 4)) != hipSuccess ||
+        (e = d_tri_mat_.reserve(tri_mat_.size() * 4)) != hipSuccess ||
+        (e = d_tri_uv_.reserve(tri_uv_.size() * 4)) != hipSuccess)
+        return hip_fail(e, "hipMalloc (scene)");
+    hipSetDevice(device_);
+    if (nb && !dev_built) e = hipMemcpyAsync(d_nodes_.p, oct_.nodes.data(), nb, hipMemcpyHostToDevice, stream_);
+    if (e == hipSuccess && tb && !dev_built)
+        e = hipMemcpyAsync(d_tris_.p, oct_.tris.data(), tb, hipMemcpyHostToDevice, stream_);
+    if (e == hipSuccess && !oct_.tri_id.empty() && !dev_built)
+        e = hipMemcpyAsync(d_tri_id_.p, oct_.tri_id.data(), oct_.tri_id.size() * 4, hipMemcpyHostToDevice, stream_);
+    if (e == hipSuccess && !tri_mat_.empty())
+        e = hipMemcpyAsync(d_tri_mat_.p, tri_mat_.data(), tri_mat_.size() * 4, hipMemcpyHostToDevice, stream_);
+    if (e == hipSuccess && !tri_uv_.empty())
+        e = hipMemcpyAsync(d_tri_uv_.p, tri_uv_.data(), tri_uv_.size() * 4, hipMemcpyHostToDevice, stream_);
+    return RT_OK;
+}
+
+// The quick wide BVH (the octree's own hierarchy, O(n): wbvh.hpp build_wbvh_quick) into wide_ while the octree
+// uploads, resident for the next frames until the SAH tree replaces it.  Not after a failed
+// upload (e), which also takes this one's failure.
+int Renderer::build_quick_wide(bool dev_built, hipError_t& e)
+{
+    const bool quick = e == hipSuccess && s_.enable_bvh && knobs_.quick_wbvh && knobs_.wbvh && !knobs_.exact && oct_nn_ > 0;
+    wb_ = WBvh();
+    wb_on_device_ = false;
+    if (quick && dev_built) {   // (the octree is in HBM: the quick tree is built from it where it lies)
+        int rc = build_wide_device(wb_on_device_);
         if (rc != RT_OK)
             return rc;
     }
-    if (mats_dirty_) {
-        if ((e = d_mats_.reserve(mats_.size() * 4)) != hipSuccess)
-            return hip_fail(e, "hipMalloc (materials)");
-        if (!mats_.empty() &&
-            (e = hipMemcpy(d_mats_.p, mats_.data(), mats_.size() * 4, hipMemcpyHostToDevice)) != hipSuccess)
-            return hip_fail(e, "upload (materials)");
-        mats_dirty_ = false;
+    if (quick && !wb_on_device_) {   // (its time counts in build_ms, the blocking part; build_split_ms[2] is the SAH tree's)
+        build_wbvh_quick(oct_, wb_, false);   // (records gathered on the device)
+        if (!wb_.nodes.empty())
+            e = upload_wide(wb_, wide_, stream_);
     }
-    if (tex_dirty_) {
-        for (int i = 0; i < TEX_SLOTS + 6; i++) {
-            HostTex& t = i < TEX_SLOTS ? tex_[i] : sky_[i - TEX_SLOTS];
-            DevBuf& d = i < TEX_SLOTS ? d_tex_[i] : d_sky_[i - TEX_SLOTS];
-            if (t.rgba.empty())
-                continue;
-            if ((e = d.reserve(t.rgba.size() * 4)) != hipSuccess)
-                return hip_fail(e, "hipMalloc (texture)");
-            if ((e = hipMemcpy(d.p, t.rgba.data(), t.rgba.size() * 4, hipMemcpyHostToDevice)) != hipSuccess)
-                return hip_fail(e, "upload (texture)");
-        }
-        tex_dirty_ = false;
+    return RT_OK;
+}
+
+int Renderer::upload_materials()
+{
+    hipError_t e;
+    if ((e = d_mats_.reserve(mats_.size() * 4)) != hipSuccess)
+        return hip_fail(e, "hipMalloc (materials)");
+    if (!mats_.empty() && (e = hipMemcpy(d_mats_.p, mats_.data(), mats_.size() * 4, hipMemcpyHostToDevice)) != hipSuccess)
+        return hip_fail(e, "upload (materials)");
+    mats_dirty_ = false;
+    return RT_OK;
+}
+
+int Renderer::upload_textures()
+{
+    hipError_t e;
+    for (int i = 0; i < TEX_SLOTS + 6; i++) {
+        HostTex& t = i < TEX_SLOTS ? tex_[i] : sky_[i - TEX_SLOTS];
+        DevBuf& d = i < TEX_SLOTS ? d_tex_[i] : d_sky_[i - TEX_SLOTS];
+        if (t.rgba.empty())
+            continue;
+        if ((e = d.reserve(t.rgba.size() * 4)) != hipSuccess)
+            return hip_fail(e, "hipMalloc (texture)");
+        if ((e = hipMemcpy(d.p, t.rgba.data(), t.rgba.size() * 4, hipMemcpyHostToDevice)) != hipSuccess)
+            return hip_fail(e, "upload (texture)");
     }
+    tex_dirty_ = false;
     return RT_OK;
 }
 
@@ -1552,9 +1590,9 @@ void Renderer::fill_params(KParams& P) const
     // was built, the scene's scale keeps the certificate's rounding margins (as for the
     // segment queries), and RT_WBVH is not 0
     if (wide_ready_ && knobs_.wbvh && !knobs_.exact && P.scene_scale > 0x1p-20f && P.scene_scale < 0x1p20f) {
-        P.wnodes = d_wnodes_.as<WNode>();
-        P.wtris = d_wtris_.as<GTri>();
-        P.wmeta = d_wmeta_.as<uint4>();
+        P.wnodes = wide_.nodes();
+        P.wtris = wide_.tris();
+        P.wmeta = wide_.meta();
         if (ocone_ready_ && knobs_.ocone) {
             P.ocone.cells = d_ocone_.as<uint2>();
             for (int a = 0; a < 3; a++) {
@@ -2343,12 +2381,12 @@ int Renderer::band_costs(hipStream_t stream, double* costs, int nbands)
     const BandSlot* S = nullptr;
     for (int i = 0; i < band_nslots_; i++)
         if (band_slot_[i].stream == stream) S = &band_slot_[i];
-    if (!S || !S->live || !S->tc.cost.p || S->tc.ntiles <= 0 || S->tc.band_rows <= 0)
+    if (!S || !S->fence.live() || !S->tc.cost.p || S->tc.ntiles <= 0 || S->tc.band_rows <= 0)
         return fail(RT_EINVAL, "band_costs: no band launch with tile costs on this stream");
     const TileCost& T = S->tc;
     if (!costs || nbands < (H + T.band_rows - 1) / T.band_rows)
         return fail(RT_EINVAL, "band_costs: buffer smaller than the image's bands");
-    hipError_t e = hipEventSynchronize(S->done);
+    hipError_t e = S->fence.sync();
     std::vector<uint32_t> c((size_t)T.ntiles);
     if (e == hipSuccess)
         e = hipMemcpy(c.data(), T.cost.p, c.size() * 4, hipMemcpyDeviceToHost);
@@ -2466,16 +2504,15 @@ int Renderer::render_bands_impl(int band_rows, int rank, int nranks, const int32
     if (si < 0) {
         if (band_nslots_ < BAND_SLOTS) {
             si = band_nslots_++;
-            if ((e = hipEventCreateWithFlags(&band_slot_[si].done, hipEventDisableTiming)) != hipSuccess ||
-                (e = hipEventCreateWithFlags(&band_slot_[si].mark, hipEventDisableTiming)) != hipSuccess)
+            if ((e = band_slot_[si].fence.create()) != hipSuccess)
                 return hip_fail(e, "hipEventCreate");
         } else {
             // a ninth stream: the least recently used slot is recycled once its last launch is
-            // done (its own event; the stream it ran on may no longer exist)
+            // done (its own fence; the stream it ran on may no longer exist)
             si = 0;
             for (int i = 1; i < BAND_SLOTS; i++)
                 if (band_slot_[i].used < band_slot_[si].used) si = i;
-            if (band_slot_[si].live && (e = hipEventSynchronize(band_slot_[si].done)) != hipSuccess)
+            if ((e = band_slot_[si].fence.sync()) != hipSuccess)
                 return hip_fail(e, "render_bands_device: recycling a stream slot");
         }
         band_slot_[si].stream = stream;
@@ -2504,7 +2541,7 @@ int Renderer::render_bands_impl(int band_rows, int rank, int nranks, const int32
         for (int i = 0; i < nbands; i++)
             host[(size_t)nbands + bands[i]] = i;
         if (host != S.map_host || nb != S.map_nb) {
-            if (S.live && (e = hipEventSynchronize(S.done)) != hipSuccess)
+            if ((e = S.fence.sync()) != hipSuccess)
                 return hip_fail(e, "render_band_list_device: waiting for the slot's last launch");
             if ((e = S.map.reserve(host.size() * 4)) != hipSuccess ||
                 (e = hipMemcpy(S.map.p, host.data(), host.size() * 4, hipMemcpyHostToDevice)) != hipSuccess)
@@ -2549,7 +2586,7 @@ int Renderer::render_bands_impl(int band_rows, int rank, int nranks, const int32
     bool zeroed = false;   // heavy_prep_kernel clears the counter words itself (one dispatch fewer)
     bool overlapped = false;   // another band launch still in flight (frames in flight)
     for (int i = 0; i < band_nslots_ && !overlapped; i++)
-        overlapped = i != si && band_slot_[i].live && hipEventQuery(band_slot_[i].done) == hipErrorNotReady;
+        overlapped = i != si && band_slot_[i].fence.busy();
     if ((rc = prepare_heavy(P, S.tc, stream, layout_key, &zeroed, overlapped)) != RT_OK)
         return rc;
     if (!zeroed && (e = hipMemsetAsync(S.counters.p, 0, NCOUNTER_WORDS * 8, stream)) != hipSuccess)
@@ -2566,20 +2603,15 @@ int Renderer::render_bands_impl(int band_rows, int rank, int nranks, const int32
     if (ring_count_ < EV_RING) ring_count_++;
     if (f > 1 && !fused && (e = rt_launch_downscale(target, P.rw, P.local_rows, f, d_out, stream)) != hipSuccess)
         return hip_fail(e, "downscale launch");
-    // 'done' is recorded on the renderer's own fence stream behind the caller's: later waits on it
-    // never touch the caller's stream, which may be destroyed by then (an event recorded on a
-    // destroyed stream made hipEventSynchronize fail with a capture-state error)
-    if ((e = hipEventRecord(S.mark, stream)) != hipSuccess || (e = hipStreamWaitEvent(fence_stream_, S.mark, 0)) != hipSuccess ||
-        (e = hipEventRecord(S.done, fence_stream_)) != hipSuccess)
+    if ((e = S.fence.record(stream, fence_stream_)) != hipSuccess)
         return hip_fail(e, "hipEventRecord");
-    S.live = true;
     return RT_OK;
 }
 
 // The frame's grazing-risk keys (KParams::wrisk, wbvh.hpp WRiskArgs): computed on
 // 'stream' when the camera, the light or the resident wide BVH changed since the last computation
 // (launches in flight on other streams read the keys: the stream first waits for them); every
-// launch waits for the computation (risk_ev_).  RT_WBVH_RISK=0: none (every child runs case (b)).
+// launch waits for the computation (risk_fence_).  RT_WBVH_RISK=0: none (every child runs case (b)).
 int Renderer::prepare_risk(KParams& P, hipStream_t stream)
 {
     P.wrisk = nullptr;
@@ -2591,12 +2623,12 @@ int Renderer::prepare_risk(KParams& P, hipStream_t stream)
     // root is the host copy's, or read back once per adopted tree where the tree was built on the device
     // (or copied from the lead device); the six floats travel by value with each launch.  RT_SCENE_BOUND=0: none
     P.sb_valid = 0;
-    if (P.wnodes && knobs_.scene_bound && risk_nodes_ > 0) {
+    if (P.wnodes && knobs_.scene_bound && wide_.nn > 0) {
         if (!sb_root_valid_) {
             if (!wb_on_device_ && !lead_ && !wb_.nodes.empty())
                 sb_root_ = wb_.nodes[0];
             else {
-                const hipError_t e = hipMemcpy(&sb_root_, d_wnodes_.p, sizeof(WNode), hipMemcpyDeviceToHost);
+                const hipError_t e = hipMemcpy(&sb_root_, wide_.nodes(), sizeof(WNode), hipMemcpyDeviceToHost);
                 if (e != hipSuccess)
                     return hip_fail(e, "download (the wide BVH's root)");
             }
@@ -2607,8 +2639,9 @@ int Renderer::prepare_risk(KParams& P, hipStream_t stream)
         std::memcpy(P.sb_hi, B.hi, sizeof P.sb_hi);
         P.sb_valid = B.valid;
     }
-    if (!P.wnodes || !knobs_.risk || risk_nodes_ <= 0 || !d_wrisk_.p || !d_wlinks_.p)
+    if (!P.wnodes || !knobs_.risk || wide_.nn <= 0 || !d_wrisk_.p || !wide_.b_links.p)
         return RT_OK;
+    const WRiskView R = wide_risk_view(d_wrisk_.p, (size_t)wide_.nn);
     // the risk caps' directions: from the camera / the light towards the scene's centre (any direction is
     // sound; this one makes a convex object's silhouette interior skip case (b), wbvh.hpp risk_cap_skip)
     float cap_dir[2][3];
@@ -2632,40 +2665,29 @@ int Renderer::prepare_risk(KParams& P, hipStream_t stream)
         const float hi[3] = {oct_root_.df[0], oct_root_.df[1], oct_root_.df[2]};
         const WRiskArgs A = wbvh_risk_args(lo, hi, P.scene_scale, P.cam_pos, P.light, W_QS_CLOSEST, W_QS_SHADOW);
         risk_valid_ = false;
-        const uint32_t* links = d_wlinks_.as<uint32_t>();
-        // d_wrisk_: the packed words (8 x 8 B per node), then the walk's keys (8 x 4 B) and boxes (8 x 24 B)
-        const size_t ne = (size_t)risk_nodes_ * 8;
-        unsigned long long* words = d_wrisk_.as<unsigned long long>();
-        uint32_t* K = reinterpret_cast<uint32_t*>(words + ne);
-        float* B = reinterpret_cast<float*>(K + ne);
-        uint32_t* cap = reinterpret_cast<uint32_t*>(B + 6 * ne);   // (the 2 caps, past the boxes)
         std::memcpy(risk_cap_dir_, cap_dir, sizeof risk_cap_dir_);
-        if ((e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(K), 0x7F800000, ne, stream)) != hipSuccess ||
-            (e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(cap), 0x7F800000, 2, stream)) != hipSuccess ||
-            (e = rt_launch_risk_box_init(B, ne, stream)) != hipSuccess ||
-            (e = rt_launch_wide_risk(P.wtris, P.wmeta, P.nodes, P.wnodes, links, links + risk_tris_, K, B, words,
-                                     (int)risk_tris_, (int)risk_nodes_, &A, cap, &risk_cap_dir_[0][0], stream)) != hipSuccess ||
-            // risk_ev_ is recorded on the renderer's own fence stream behind 'stream' (as a band slot's
-            // 'done'): later launches wait on it after the caller may have destroyed 'stream'
-            (e = hipEventRecord(risk_mark_, stream)) != hipSuccess ||
-            (e = hipStreamWaitEvent(fence_stream_, risk_mark_, 0)) != hipSuccess ||
-            (e = hipEventRecord(risk_ev_, fence_stream_)) != hipSuccess)
+        if ((e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(R.keys), 0x7F800000, R.entries, stream)) != hipSuccess ||
+            (e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(R.caps), 0x7F800000, 2, stream)) != hipSuccess ||
+            (e = rt_launch_risk_box_init(R.boxes, R.entries, stream)) != hipSuccess ||
+            (e = rt_launch_wide_risk(P.wtris, P.wmeta, P.nodes, P.wnodes, wide_.tri_leaf(), wide_.parent(), R.keys, R.boxes,
+                                     R.words, (int)wide_.nt, (int)wide_.nn, &A, R.caps, &risk_cap_dir_[0][0], stream)) !=
+                hipSuccess ||
+            (e = risk_fence_.record(stream, fence_stream_)) != hipSuccess)
             return hip_fail(e, "wide_risk_kernel");
-        risk_ev_live_ = true;
         risk_valid_ = true;
         std::memcpy(risk_cam_, P.cam_pos, sizeof risk_cam_);
         std::memcpy(risk_light_, P.light, sizeof risk_light_);
         risk_G_ = A.ray_G;
         risk_nl_ = A.ray_nl;
         risk_nu_ = A.ray_nu;
-    } else if (risk_ev_live_ && (e = hipStreamWaitEvent(stream, risk_ev_, 0)) != hipSuccess)
+    } else if ((e = risk_fence_.wait_on(stream)) != hipSuccess)
         return hip_fail(e, "hipStreamWaitEvent (risk bits)");
-    P.wrisk = d_wrisk_.as<uint64_t>();
+    P.wrisk = reinterpret_cast<const uint64_t*>(R.words);
     P.risk_G = risk_G_;
     P.risk_nl = risk_nl_;
     P.risk_nu = risk_nu_;
     if (knobs_.risk_cap) {
-        P.risk_cap = reinterpret_cast<const float*>(d_wrisk_.as<uint8_t>() + (size_t)risk_nodes_ * 288);
+        P.risk_cap = reinterpret_cast<const float*>(R.caps);
         std::memcpy(P.cap_dir, risk_cap_dir_, sizeof P.cap_dir);
     }
     return RT_OK;
@@ -2673,7 +2695,7 @@ int Renderer::prepare_risk(KParams& P, hipStream_t stream)
 
 // The tile mask (KParams::tile_mask, wbvh.hpp wbvh_mask_rect) of a frame launch.  The cut is
 // computed once per resident tree (the computing stream first waits for the launches in flight, whose mask
-// kernels may read the old one; every other stream's mask kernel waits for it, mask_ev_).  The mask is the
+// kernels may read the old one; every other stream's mask kernel waits for it, cut_fence_).  The mask is the
 // launching stream's own (M): recomputed on that stream, ahead of the frame, when the camera's matrices, the
 // render size, the light's finiteness or the cut changed since the stream's last launch -- the stream's
 // earlier launches read the old words before it, and no other stream reads them, so a moving camera keeps
@@ -2685,7 +2707,7 @@ int Renderer::prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M)
     P.mask_wpr = 0;
     mask_last_ = nullptr;
     mask_seen_ = true;
-    if (!knobs_.tile_mask || !P.wnodes || !P.plain || P.has_reflection || P.zbuf || P.nbuf || risk_nodes_ <= 0 || !d_wlinks_.p ||
+    if (!knobs_.tile_mask || !P.wnodes || !P.plain || P.has_reflection || P.zbuf || P.nbuf || wide_.nn <= 0 || !wide_.b_links.p ||
         s_.hybrid_rasterization_tracing)
         return RT_OK;
     const WMaskCam C = wbvh_mask_cam(P.proj_inv, P.cam_to_world, P.proj_mode, P.proj_w, P.c2w_affine, P.cam_pos, P.light,
@@ -2698,13 +2720,10 @@ int Renderer::prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M)
             return RT_EHIP;
         if ((e = d_cut_.reserve((size_t)(2 * W_CUT_MAX + 1) * 4)) != hipSuccess)
             return hip_fail(e, "hipMalloc (tile mask cut)");
-        if ((e = rt_launch_wide_cut(P.wnodes, (int)risk_nodes_, knobs_.cut_budget, W_CUT_DEPTH, d_cut_.as<uint32_t>(), stream)) !=
+        if ((e = rt_launch_wide_cut(P.wnodes, (int)wide_.nn, knobs_.cut_budget, W_CUT_DEPTH, d_cut_.as<uint32_t>(), stream)) !=
                 hipSuccess ||
-            (e = hipEventRecord(mask_mark_, stream)) != hipSuccess ||
-            (e = hipStreamWaitEvent(fence_stream_, mask_mark_, 0)) != hipSuccess ||
-            (e = hipEventRecord(mask_ev_, fence_stream_)) != hipSuccess)
+            (e = cut_fence_.record(stream, fence_stream_)) != hipSuccess)
             return hip_fail(e, "wide_cut_kernel");
-        mask_ev_live_ = true;
         cut_valid_ = true;
         cut_gen_++;
     }
@@ -2712,8 +2731,8 @@ int Renderer::prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M)
         M.cut_gen = 0;
         if ((e = M.words.reserve((size_t)C.bh * C.wpr * 4)) != hipSuccess)
             return hip_fail(e, "hipMalloc (tile mask)");
-        if ((mask_ev_live_ && (e = hipStreamWaitEvent(stream, mask_ev_, 0)) != hipSuccess) ||
-            (e = rt_launch_wide_mask(P.wnodes, (int)risk_nodes_, d_wlinks_.as<uint32_t>() + risk_tris_, d_cut_.as<uint32_t>(),
+        if ((e = cut_fence_.wait_on(stream)) != hipSuccess ||
+            (e = rt_launch_wide_mask(P.wnodes, (int)wide_.nn, wide_.parent(), d_cut_.as<uint32_t>(),
                                      knobs_.cut_budget, &C, M.words.as<uint32_t>(), stream)) != hipSuccess)
             return hip_fail(e, "wide_mask_kernel");
         M.cut_gen = cut_gen_;
@@ -2809,9 +2828,9 @@ int Renderer::wait_slots(hipStream_t stream)
 {
     for (int i = 0; i < band_nslots_; i++) {
         BandSlot& b = band_slot_[i];
-        if (!b.live || b.stream == stream)
+        if (b.stream == stream)
             continue;
-        hipError_t e = hipStreamWaitEvent(stream, b.done, 0);
+        hipError_t e = b.fence.wait_on(stream);
         if (e != hipSuccess)
             return hip_fail(e, "hipStreamWaitEvent (frames in flight)");
     }
@@ -2821,10 +2840,7 @@ int Renderer::wait_slots(hipStream_t stream)
 int Renderer::sync_slots()
 {
     for (int i = 0; i < band_nslots_; i++) {
-        BandSlot& b = band_slot_[i];
-        if (!b.live)
-            continue;
-        hipError_t e = hipEventSynchronize(b.done);
+        hipError_t e = band_slot_[i].fence.sync();
         if (e != hipSuccess)
             return hip_fail(e, "hipEventSynchronize (frames in flight)");
     }
@@ -2946,9 +2962,9 @@ int Renderer::risk_words(int src, uint64_t* out, int64_t cap, int64_t* count, in
         return rc;
     KParams P;
     fill_params(P);
-    if (!P.wnodes || !knobs_.risk || risk_nodes_ <= 0)
+    if (!P.wnodes || !knobs_.risk || wide_.nn <= 0)
         return fail(RT_ESTATE, "risk_words: no wide BVH with risk words (exact mode, RT_WBVH=0 or RT_WBVH_RISK=0)");
-    const int64_t ne = risk_nodes_ * 8;
+    const int64_t ne = wide_.nn * (int64_t)WRISK_ENTRIES;
     *count = ne;
     if (!out)
         return RT_OK;
@@ -3089,7 +3105,7 @@ int Renderer::band_counters(unsigned long long out[2])
     unsigned long long cnt[NCOUNTERS] = {};
     if (band_last_ < 0)
         return fail(RT_ESTATE, "band_counters: no render_bands_device launch yet");
-    hipError_t e = hipEventSynchronize(band_slot_[band_last_].done);
+    hipError_t e = band_slot_[band_last_].fence.sync();
     if (e == hipSuccess)
         e = hipMemcpy(cnt, band_slot_[band_last_].counters.p, sizeof(cnt), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail(e, "band_counters");
@@ -3140,12 +3156,11 @@ int Renderer::tile_mask(int src, uint32_t* out, int64_t cap, int32_t info[5])
         return hip_fail(e, "tile_mask");
     info[4] = (int32_t)ncut;
     if (src == 1) {
-        std::vector<WNode> nodes((size_t)risk_nodes_);
-        if ((e = hipMemcpy(nodes.data(), d_wnodes_.p, nodes.size() * sizeof(WNode), hipMemcpyDeviceToHost)) != hipSuccess)
+        std::vector<WNode> nodes((size_t)wide_.nn);
+        if ((e = hipMemcpy(nodes.data(), wide_.nodes(), nodes.size() * sizeof(WNode), hipMemcpyDeviceToHost)) != hipSuccess)
             return hip_fail(e, "download (wide BVH nodes)");
         std::vector<uint32_t> cut, words, parent(nodes.size());
-        if ((e = hipMemcpy(parent.data(), d_wlinks_.as<uint32_t>() + risk_tris_, parent.size() * 4, hipMemcpyDeviceToHost)) !=
-            hipSuccess)
+        if ((e = hipMemcpy(parent.data(), wide_.parent(), parent.size() * 4, hipMemcpyDeviceToHost)) != hipSuccess)
             return hip_fail(e, "download (wide BVH parents)");
         wbvh_cut_host(nodes.data(), (int64_t)nodes.size(), knobs_.cut_budget, W_CUT_DEPTH, W_QS_CLOSEST, cut);
         wbvh_mask_host(nodes.data(), (int64_t)nodes.size(), parent.data(), cut, mask_last_->cam, words);

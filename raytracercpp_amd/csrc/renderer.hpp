@@ -20,6 +20,7 @@
 #include "ocone.hpp"
 #include "octree.hpp"
 #include "wbvh.hpp"
+#include "wide_layout.hpp"
 
 namespace rt {
 
@@ -42,6 +43,68 @@ struct DevBuf {
         std::swap(bytes, o.bytes);
         std::swap(device, o.device);
     }
+};
+
+// The device-resident wide BVH (wbvh.hpp) as one value: the nodes, the triangle records in its leaf order and
+// their metadata (what frames read), the slot maps wide_gather_kernel reads (tmp) and the grazing-risk walk's
+// links, with the counts they were sized for (0: no tree).  The offsets inside tmp and links are
+// wide_layout.hpp's.  The renderer holds two: the resident tree, and the background build's, which only
+// accel_thread_ writes until adoption swaps them.
+struct WideDev {
+    DevBuf b_nodes, b_tris, b_meta, b_tmp, b_links;
+    int64_t nn = 0, nt = 0;   // nodes, triangle records
+    WNode* nodes() const { return b_nodes.as<WNode>(); }
+    GTri* tris() const { return b_tris.as<GTri>(); }
+    uint4* meta() const { return b_meta.as<uint4>(); }
+    int32_t* slot() const { return at<int32_t>(b_tmp, wide_tmp_slot_off((size_t)nn, (size_t)nt)); }
+    uint32_t* leaf_of_slot() const { return at<uint32_t>(b_tmp, wide_tmp_leaf_of_slot_off((size_t)nn, (size_t)nt)); }
+    uint32_t* tri_leaf() const { return at<uint32_t>(b_links, wide_links_tri_leaf_off((size_t)nn, (size_t)nt)); }
+    uint32_t* parent() const { return at<uint32_t>(b_links, wide_links_parent_off((size_t)nn, (size_t)nt)); }
+    // sizes the five buffers for a tree of these counts (the counts are the tree's from here on)
+    hipError_t reserve(int64_t nodes, int64_t tris);
+    void clear() { nn = nt = 0; }   // no tree (the allocations are kept for the next one)
+    void swap(WideDev& o);
+
+private:
+    template <class T> static T* at(const DevBuf& b, size_t off) { return reinterpret_cast<T*>(b.as<char>() + off); }
+};
+
+// "Everything launched on a stream up to here has finished", for waits that may come after the caller has
+// destroyed that stream: 'mark' is recorded on the caller's stream, the renderer's own fence stream waits
+// on it, and 'done' is recorded there.  Later waits touch only 'done' (an event recorded on a stream that
+// was destroyed since made hipEventSynchronize fail with a capture-state error).  Waits before the first
+// record() pass at once.
+struct Fence {
+    hipError_t create()
+    {
+        hipError_t e = hipEventCreateWithFlags(&done_, hipEventDisableTiming);
+        return e == hipSuccess ? hipEventCreateWithFlags(&mark_, hipEventDisableTiming) : e;
+    }
+    void destroy()
+    {
+        if (done_) hipEventDestroy(done_);
+        if (mark_) hipEventDestroy(mark_);
+        done_ = mark_ = nullptr;
+        live_ = false;
+    }
+    hipError_t record(hipStream_t stream, hipStream_t fence_stream)
+    {
+        hipError_t e;
+        if ((e = hipEventRecord(mark_, stream)) == hipSuccess && (e = hipStreamWaitEvent(fence_stream, mark_, 0)) == hipSuccess &&
+            (e = hipEventRecord(done_, fence_stream)) == hipSuccess)
+            live_ = true;
+        return e;
+    }
+    // 'stream', or the host, waits for the last record()
+    hipError_t wait_on(hipStream_t stream) const { return live_ ? hipStreamWaitEvent(stream, done_, 0) : hipSuccess; }
+    hipError_t sync() const { return live_ ? hipEventSynchronize(done_) : hipSuccess; }
+    bool live() const { return live_; }   // record() has been called
+    // what the last record() follows is still running
+    bool busy() const { return live_ && hipEventQuery(done_) == hipErrorNotReady; }
+
+private:
+    hipEvent_t mark_ = nullptr, done_ = nullptr;
+    bool live_ = false;
 };
 
 struct HostTex {
@@ -234,6 +297,13 @@ private:
     void render_size(int& w, int& h) const;
     void update_camera_projection();
     int ensure_device_scene();
+    // a geometry change on the lead (a helper's: adopt_from_lead) and its steps, in order
+    int rebuild_geometry();
+    int build_octree(int64_t n, bool& dev_built);
+    int upload_octree_tables(bool dev_built, hipError_t& e);
+    int build_quick_wide(bool dev_built, hipError_t& e);
+    int upload_materials();
+    int upload_textures();
     int validate() const;
     void fill_params(KParams& P) const;
     // the trace of one launch: the ray-trace kernel, or the reflection engine (frames by level)
@@ -273,11 +343,19 @@ private:
     float oc_ms_ = 0.0f;                // the origin cones' build (background, after the tree)
     std::string accel_err_;
     hipStream_t accel_stream_ = nullptr;
-    hipStream_t fence_stream_ = nullptr;   // the band slots' 'done' events (render_bands_device)
+    hipStream_t fence_stream_ = nullptr;   // every Fence's 'done' event is recorded here
     float accel_ms_[3] = {};            // cones + slabs, wide BVH, wide-BVH upload (background)
     bool cones_ready_ = false, wide_ready_ = false, lslab_ready_ = false;
     int wide_tree_ = 0;   // rt_stats.wide_tree: 0 none, 1 the quick tree, 2 the SAH tree, -1 its build failed
-    uint64_t accel_ver_ = 0;   // bumped when poll_accel adopts a build
+    uint64_t accel_ver_ = 0;   // bumped by install_wide: what a helper has copied (mir_accel_)
+    // The one place a tree becomes resident (wide_, already written: the quick tree after a geometry change,
+    // the SAH tree at adoption, a helper's copy of its lead's; wide_.nn == 0: the build left none).  Sets
+    // wide_ready_ and wide_tree_ (tree, or 0 without one), sizes the risk buffer, invalidates what was derived
+    // from the tree before (the risk words, the scene bound's root, the tile mask's cut), bumps accel_ver_.
+    int install_wide(int tree);
+    // The one place the geometry's acceleration structures are dropped (a geometry change, on the lead and on
+    // a helper): frames take the exact octree path until the next install_wide.
+    void drop_accel();
     void start_accel();
     // release: adopt even under RT_ACCEL_HOLD (rt_finish_accel, and before the geometry is replaced)
     int poll_accel(bool wait, bool release = false);
@@ -299,8 +377,8 @@ private:
     // builder does not take the input (the caller builds on the host)
     int build_octree_device(int64_t n, bool& built);
     // the quick wide BVH of a device-built octree, built there too (wbvh_quick_gpu.hpp):
-    // d_wnodes_ / d_wtris_ / d_wmeta_ / d_wlinks_ written in place.  wb_ then stays empty (wb_on_device_)
-    // until a host reader asks for it (host_wide: one download); the counts are risk_nodes_ / risk_tris_.
+    // wide_ written in place.  wb_ then stays empty (wb_on_device_) until a host reader asks for it
+    // (host_wide: one download).
     int64_t device_wide_builds_ = 0;
     std::unique_ptr<OctreeDevInfo> oct_dev_info_;   // the last device octree build's totals
     std::unique_ptr<WQuickGpuScratch> wq_gpu_;
@@ -396,43 +474,39 @@ private:
     DevBuf d_lslab_;
     std::vector<float> lsin_;   // per leaf (at its first slot): <= sin(angle at a) of its triangles
     DevBuf d_lsin_;
-    // the wide BVH (wbvh.hpp): nodes, triangle records in its leaf order, slot maps
+    // the resident wide BVH (wbvh.hpp): its host copy and its device buffers
     WBvh wb_;
-    DevBuf d_wnodes_, d_wtris_, d_wmeta_;
-    DevBuf d_wtmp_;   // the wide BVH's slot map and the octree's slot -> leaf map, for wide_gather_kernel
-    // the background build's tree and buffers (start_accel), swapped in at adoption (poll_accel): the
-    // resident tree may be the quick one (wbvh.hpp build_wbvh_quick) that frames in flight still read
+    WideDev wide_;
+    // the background build's (start_accel: accel_thread_ writes only these), swapped in at adoption
+    // (poll_accel): the resident tree may be the quick one (wbvh.hpp build_wbvh_quick) that frames in flight
+    // still read
     WBvh wb_next_;
-    DevBuf d_wnodes2_, d_wtris2_, d_wmeta2_, d_wtmp2_, d_wlinks2_;
+    WideDev wide_next_;
     // the origin cones (ocone.hpp) of the resident SAH tree's triangles and the background build's
     OConeGrid ocg_, ocg_next_;
     DevBuf d_ocone_, d_ocone2_, d_oc_ent_, d_oc_todo_;
     bool ocone_ready_ = false;
     float risk_cap_dir_[2][3] = {};   // the risk caps' directions of the resident words (camera, light)
-    // a wide BVH's upload into the given buffers on 'stream' (the gather of its triangle records and
-    // metadata from the resident octree tables on the device)
-    hipError_t upload_wide(const WBvh& w, DevBuf& nodes, DevBuf& tris, DevBuf& meta, DevBuf& tmp, DevBuf& links,
-                           hipStream_t stream);
+    // a wide BVH's upload into d on 'stream' (the gather of its triangle records and metadata from the
+    // resident octree tables on the device)
+    hipError_t upload_wide(const WBvh& w, WideDev& d, hipStream_t stream);
     int reserve_risk(size_t nodes);
-    // the grazing-risk keys (KParams::wrisk): the walk's links (WBvh::tri_leaf then parent), the keys,
-    // and the camera / light / structure they were computed for; risk_ev_ follows their launch
-    DevBuf d_wlinks_, d_wrisk_;
+    // the grazing-risk keys (KParams::wrisk; the buffer's layout: wide_layout.hpp), and the camera / light /
+    // structure they were computed for; risk_fence_ follows their launch
+    DevBuf d_wrisk_;
     bool risk_valid_ = false;
     // the resident wide BVH's root, for the scene bound (prepare_risk); false after every change of tree
     WNode sb_root_{};
     bool sb_root_valid_ = false;
-    int64_t risk_nodes_ = 0, risk_tris_ = 0;   // the resident wide BVH's node and triangle counts
     float risk_cam_[3] = {0, 0, 0}, risk_light_[3] = {0, 0, 0};
     float risk_G_ = 0.0f, risk_nl_ = 0.0f, risk_nu_ = 0.0f;
-    hipEvent_t risk_ev_ = nullptr;     // recorded on fence_stream_ behind the computation
-    hipEvent_t risk_mark_ = nullptr;   // recorded on the computing stream (fence_stream_ waits on it)
-    bool risk_ev_live_ = false;
+    Fence risk_fence_;
     // sets P.wrisk (and risk_G / risk_nl) for the frame's camera and light, recomputing the bits on
     // 'stream' when they changed; every launch that reads them waits for their computation
     int prepare_risk(KParams& P, hipStream_t stream);
     // the tile mask (wbvh.hpp wbvh_mask_rect): the resident tree's cut (d_cut_: 2 W_CUT_MAX + 1
-    // words; false after every change of tree, as sb_root_valid_; mask_ev_ follows its computation, as
-    // risk_ev_ the risk words') and, per launching stream, the mask of that stream's last camera: a launch
+    // words; false after every change of tree, as sb_root_valid_; cut_fence_ follows its computation, as
+    // risk_fence_ the risk words') and, per launching stream, the mask of that stream's last camera: a launch
     // computes its mask on its own stream, so a moving camera does not make the frames in flight wait for
     // each other.  mask_last_: the mask the last launch was given (nullptr: none).
     struct MaskSlot {
@@ -441,11 +515,11 @@ private:
         uint64_t cut_gen = 0;  // and the cut (0: no words yet)
     };
     DevBuf d_cut_;
-    bool cut_valid_ = false, mask_ev_live_ = false, mask_seen_ = false;
+    bool cut_valid_ = false, mask_seen_ = false;
     uint64_t cut_gen_ = 0;
     MaskSlot mask_main_;       // rt_ray_trace's (stream_)
     MaskSlot* mask_last_ = nullptr;
-    hipEvent_t mask_ev_ = nullptr, mask_mark_ = nullptr;
+    Fence cut_fence_;
     int prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M);
     DevBuf d_dbg_;                          // diagnostic per-wave records (RT_DEBUG_WAVES)
     bool ssao_ready_ = false;   // the buffers hold the last frame's z / normals
@@ -482,8 +556,8 @@ private:
     // render_bands_device: per-stream tile-queue counters and SSAA band buffers, so that
     // frames launched on different streams can be in flight together.  Each
     // slot owns an event recorded after its last launch: launches that use buffers shared
-    // across launches (reflection engine, raster path) and scene uploads wait on every live
-    // slot's event, never on a stored stream handle (the caller may have destroyed it).
+    // across launches (reflection engine, raster path) and scene uploads wait on every
+    // slot's fence, never on a stored stream handle (the caller may have destroyed it).
     // heavy tiles first (KParams::tile_cost / heavy_list): the last launch's tile costs of a layout
     struct TileCost {
         DevBuf cost, heavy;
@@ -505,9 +579,7 @@ private:
         hipStream_t stream = nullptr;
         DevBuf counters, tmp;
         TileCost tc;
-        hipEvent_t done = nullptr;   // recorded on fence_stream_ behind the slot's last launch
-        hipEvent_t mark = nullptr;   // recorded on 'stream' after that launch (fence_stream_ waits on it)
-        bool live = false;           // 'done' has been recorded
+        Fence fence;                 // follows the slot's last launch
         DevBuf map;                  // the band list of the slot's last list launch: map, then inverse
         std::vector<int32_t> map_host;
         int map_nb = 0;              // global bands of that list's image

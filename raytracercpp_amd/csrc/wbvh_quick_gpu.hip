@@ -406,7 +406,6 @@ int build_wbvh_quick_device(WQuickGpuScratch& S, const GNode* d_nodes, const GTr
         WQ_CK(hipHostMalloc(&S.pinned, sizeof(WQuickDevInfo), hipHostMallocDefault));
     WQ_CK(S.sub.reserve((size_t)nn * 20));
     WQ_CK(S.info.reserve(sizeof(WQuickDevInfo)));
-    WQ_CK(tmp.reserve((size_t)nt * 8));
     Sub sub;
     sub.W = S.sub.as<uint32_t>();
     sub.T = sub.W + nn;
@@ -436,12 +435,17 @@ int build_wbvh_quick_device(WQuickGpuScratch& S, const GNode* d_nodes, const GTr
     WQ_CK(S.agg.reserve((size_t)np * sizeof(QChild)));
     WQ_CK(S.list.reserve((size_t)np * 4));
     WQ_CK(wnodes.reserve((size_t)np * sizeof(WNode)));
-    WQ_CK(links.reserve(((size_t)nt + (size_t)np) * 4));
+    // the arrays inside tmp and links (wide_layout.hpp)
+    const size_t lnn = (size_t)np, lnt = (size_t)nt;
+    WQ_CK(tmp.reserve(wide_tmp_bytes(lnn, lnt)));
+    WQ_CK(links.reserve(wide_links_bytes(lnn, lnt)));
+    uint32_t* const tri_leaf = reinterpret_cast<uint32_t*>(links.as<char>() + wide_links_tri_leaf_off(lnn, lnt));
+    uint32_t* const parent = reinterpret_cast<uint32_t*>(links.as<char>() + wide_links_parent_off(lnn, lnt));
     PlanOut po;
     po.plans = S.plans.as<QPlan>();
     po.np = np;
-    po.slot = tmp.as<int32_t>();
-    po.leaf_of_slot = reinterpret_cast<uint32_t*>(po.slot + nt);
+    po.slot = reinterpret_cast<int32_t*>(tmp.as<char>() + wide_tmp_slot_off(lnn, lnt));
+    po.leaf_of_slot = reinterpret_cast<uint32_t*>(tmp.as<char>() + wide_tmp_leaf_of_slot_off(lnn, lnt));
     po.nt = nt;
     po.info = d_info;
     // plans, top level first
@@ -493,8 +497,7 @@ int build_wbvh_quick_device(WQuickGpuScratch& S, const GNode* d_nodes, const GTr
         WQ_LAUNCHED();
     }
     WQ_CK(phase("geometry"));
-    wq_links_kernel<<<blocks(np), BLOCK, 0, stream>>>(wnodes.as<WNode>(), np, nt, links.as<uint32_t>(),
-                                                      links.as<uint32_t>() + nt);
+    wq_links_kernel<<<blocks(np), BLOCK, 0, stream>>>(wnodes.as<WNode>(), np, nt, tri_leaf, parent);
     WQ_LAUNCHED();
     WQ_CK(hipStreamSynchronize(stream));
     WQ_CK(phase("links"));

@@ -36,9 +36,9 @@ struct WQuickGpuScratch {
 bool wbvh_quick_device_supported(int64_t n, int max_depth);
 
 // Builds the quick tree of the device-resident octree (d_nodes / d_tris, described by oi, the host copy
-// of its OctreeDevInfo) on 'stream' and waits for it: wnodes = the WNode array, tmp = slot[] then
-// leaf_of_slot[] (oi.tris entries each, what rt_launch_wide_gather reads), links = tri_leaf[] then
-// parent[].  stats: WStats' nodes, leaves, tris, max_leaf, depth.  An empty octree is the empty tree (no
+// of its OctreeDevInfo) on 'stream' and waits for it: wnodes = the WNode array, tmp = the slot maps
+// (what rt_launch_wide_gather reads) and links = the risk walk's, both laid out by wide_layout.hpp for
+// (stats[0], stats[2]): the three buffers of a renderer.hpp WideDev.  stats: WStats' nodes, leaves, tris, max_leaf, depth.  An empty octree is the empty tree (no
 // launch).  Returns OCT_GPU_OK / OCT_GPU_UNSUPPORTED / OCT_GPU_HIP (*err: the HIP error).
 int build_wbvh_quick_device(WQuickGpuScratch& S, const GNode* d_nodes, const GTri* d_tris, const OctreeDevInfo& oi,
                             DevBuf& wnodes, DevBuf& tmp, DevBuf& links, int64_t stats[5], hipStream_t stream,
