@@ -1210,15 +1210,6 @@ int rt_wbvh_quick_build_device(int32_t device, const float* tri9, int64_t n, int
     }
 }
 
-#if defined(W_DIAG) && !defined(__HIP_DEVICE_COMPILE__)
-// host diagnostic counters of wbvh_closest (W_DIAG builds): read and reset
-__attribute__((visibility("default"))) void rt_diag_read(long long* out)
-{
-    for (int i = 0; i < 8; i++)
-        out[i] = rt::g_wdiag[i].exchange(0);
-}
-#endif
-
 int rt_wbvh_query(const float* tri9, int64_t n, int32_t max_depth, int32_t leaf_max_obj_count, const float* orig,
                   const float* dir, int64_t nrays, int32_t* status, int32_t* id, float* t, float* u, float* v,
                   int64_t stats[8], float* ms)

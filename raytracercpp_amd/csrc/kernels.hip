@@ -2453,9 +2453,6 @@ __device__ __forceinline__ void refl_no_ray(const ReflArgs& A, int slot, v3 dir)
     A.hit[slot] = H;
 }
 
-#ifndef RT_REFL_G
-#define RT_REFL_G 1   // lanes per reflection sample in refl_trace_kernel
-#endif
 #ifndef RT_OCC_REFL
 #define RT_OCC_REFL 4   // waves per SIMD of the reflection trace / shadow / pass1 kernels (r04, the sound query:
                         // C5 689 vs 656 Mrays/s at 5 (31 spills), 691 at 3; r03: 4 -> 5 about -0.6%)
@@ -2508,20 +2505,18 @@ __global__ __launch_bounds__(BLOCK, RT_OCC_REFL) void refl_trace_kernel(KParams 
     const KParams& P = kernel_params();
     (void)P_arg;
     uint2* lv = lane_stack();
-    constexpr int G = RT_REFL_G;   // lanes per sample (the launch has G threads per slot)
-    const bool lead = G == 1 || (threadIdx.x & (G - 1)) == 0;
-    int slot = (int)((blockIdx.x * BLOCK + threadIdx.x) / G);
+    int slot = (int)(blockIdx.x * BLOCK + threadIdx.x);   // one lane per sample
     int nslot = (A.c1 - A.c0) * A.stride;
     unsigned count = 0;
     v3 dir = mk(0, 0, 0);
     bool ray = slot < nslot && refl_gen(P, A, slot, dir, count);
-    wave_count_add(&P.counters[1], lead ? count : 0u);
+    wave_count_add(&P.counters[1], count);
     if (!ray) {
-        if (slot < nslot && lead)
+        if (slot < nslot)
             refl_no_ray(A, slot, dir);
         return;
     }
-    refl_trace_one<G>(P, A, slot, dir, lv, (uint32_t)A.max_steps);
+    refl_trace_one<1>(P, A, slot, dir, lv, (uint32_t)A.max_steps);
 }
 
 // Lane refill for the reflection queries (ReflArgs::feed; Aila and Laine's persistent threads with
@@ -2800,10 +2795,8 @@ __device__ __forceinline__ void refl_shadow_done(const KParams& P, const ReflArg
     A.res[slot] = make_float4(c.r, c.g, c.b, __int_as_float(child));
 }
 
-// shadow: is_shadowed (renderer.cpp:340-402) for every shaded sample (via the list)
-#ifndef RT_REFL_SHADOW_CALL
-#define RT_REFL_SHADOW_CALL 1   // the shadow pass's octree fallback out of line (octree_query_call)
-#endif
+// shadow: is_shadowed (renderer.cpp:340-402) for every shaded sample (via the list), its octree
+// fallback out of line (octree_query_call)
 __global__ __launch_bounds__(BLOCK, RT_OCC_REFL) void refl_shadow_kernel(KParams P_arg, ReflArgs A)
 {
     const KParams& P = kernel_params();
@@ -2814,7 +2807,7 @@ __global__ __launch_bounds__(BLOCK, RT_OCC_REFL) void refl_shadow_kernel(KParams
         return;
     const SampleRec& S = A.sm[A.list[t]];
     v3 light = mk(P.light[0], P.light[1], P.light[2]);
-    const bool sh = is_shadowed<false, 1, RT_REFL_SHADOW_CALL != 0>(P, ld3(S.ip), ld3(S.nrm), light, lv);
+    const bool sh = is_shadowed<false, 1, true>(P, ld3(S.ip), ld3(S.nrm), light, lv);
     // the slot read again (the list is not written here): held across the query's calls it cost 2 more
     // spilled VGPRs, 888 against 872 B of scratch (ROCm 7.2, clang 22)
     refl_shadow_done(P, A, A.list[t], sh);
@@ -3800,9 +3793,6 @@ hipError_t rt_launch_trace_colors(const rt::KParams* P, bool refl, const float* 
 // block 0 clears the launch's counter words, the sums the coming launch accumulates (stats_next) and the
 // counts of the slot's next heavy_prep (ctr_next; ctr was cleared by the previous one).  r05 ran this
 // as one 1,024-thread block: 83-91 us per launch at C4.
-#ifndef RT_HEAVY_PRIO
-#define RT_HEAVY_PRIO 1   // heavy tiles at raised wave priority (set_wave_prio)
-#endif
 __global__ __launch_bounds__(64) void heavy_prep_kernel(uint32_t* __restrict__ cost, int ntiles, int32_t* list,
                                                         uint32_t* bits, int32_t* ctr, int32_t* ctr_next,
                                                         const unsigned long long* stats_prev,
@@ -3846,8 +3836,8 @@ __global__ __launch_bounds__(64) void heavy_prep_kernel(uint32_t* __restrict__ c
     const int k = two ? base2 + __popcll(b2 & below) : base1 + __popcll(b1 & below);
     const bool listed = heavy && k < cap;
     if (listed) {
-        // the wave's issue priority while it traces the tile (bits 28-29, ray_trace_kernel)
-        const int prio = !RT_HEAVY_PRIO || ntiles >= (1 << 28) ? 0 : c >= mx / 2 ? 3 : c >= mx / 4 ? 2 : 1;
+        // the wave's issue priority while it traces the tile (bits 28-29, ray_trace_kernel; set_wave_prio)
+        const int prio = ntiles >= (1 << 28) ? 0 : c >= mx / 2 ? 3 : c >= mx / 4 ? 2 : 1;
         list[two ? cap + k : k] = i | (prio << 28);
         if (two)
             cost[i] = 0u;   // (the parts add theirs; ray_trace_kernel stores a tile's own)
@@ -4158,7 +4148,7 @@ hipError_t rt_launch_refl_stage(rt::ReflStage stage, const rt::KParams* P, const
                                dim3(rt::BLOCK), (size_t)std::max(P->levels, rt::W_STACK_REFL_FEED) * rt::BLOCK * sizeof(uint2),
                                stream, *P, *A);
         else
-            hipLaunchKernelGGL(rt::refl_trace_kernel, dim3(gs.x * RT_REFL_G), dim3(rt::BLOCK), lds, stream, *P, *A);
+            hipLaunchKernelGGL(rt::refl_trace_kernel, gs, dim3(rt::BLOCK), lds, stream, *P, *A);
         break;
     case rt::ReflStage::long_:
         hipLaunchKernelGGL(rt::refl_trace_long_kernel, dim3(std::min<unsigned>(gs.x, 2048u)), dim3(rt::BLOCK), lds, stream,

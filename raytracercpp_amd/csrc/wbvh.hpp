@@ -42,7 +42,6 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <vector>
 
@@ -53,9 +52,6 @@ namespace rt {
 constexpr uint32_t W_LEAF = 0x80000000u;
 constexpr uint32_t W_EMPTY = 0xFFFFFFFFu;
 constexpr int W_MAX_LEAF = 8;
-#ifndef W_GROUP_ILP
-#define W_GROUP_ILP 0   // lane groups: the four children's tests interleaved by the scheduler (wbvh_closest)
-#endif
 #ifndef W_STACK_N
 #define W_STACK_N 16
 #endif
@@ -78,44 +74,8 @@ constexpr int W_WIDTH = 4;    // children per node
 #define W_QS_SHADOW 0x1p-12f
 #endif
 
-// case (b)'s D (wbvh_closest): the farthest corner of the child's box (sound either way; 0: the node's
-// frame for every ray, 1: per child for rays without risk words, 2: per child for every ray)
-#ifndef W_B_CHILD_D
-#define W_B_CHILD_D 2
-#endif
-#ifndef W_A_CHILD_D
-#define W_A_CHILD_D 0   // case (a)'s D per child as well (sound either way)
-#endif
-
-// timing-only switches (tools/variants.py; never sound when off)
-#ifndef W_CASE_B
-#define W_CASE_B 1
-#endif
-#ifndef W_STEP_CAP
-#define W_STEP_CAP 0
-#endif
-#ifndef W_LAZY_EXT2
-#define W_LAZY_EXT2 0
-#endif
-#ifndef W_PRIO_ORDER
-#define W_PRIO_ORDER 1   // children visited by their unwidened entry t (wbvh_closest)
-#endif
-#ifndef W_SOUND_A
-#define W_SOUND_A 1
-#endif
 #ifndef W_SMIN_FLOOR
 #define W_SMIN_FLOOR 0.0f   // (diagnostic builds: a floor on the children's smin, to price the slivers' widening)
-#endif
-#ifndef W_R_SCALE
-#define W_R_SCALE 1.0f      // (diagnostic builds: case (a)'s widening R scaled, to price its constants)
-#endif
-
-// host diagnostic counters (tools/variants.py build diag="-DW_DIAG=1"; rt_diag_read)
-#if defined(W_DIAG) && !defined(__HIP_DEVICE_COMPILE__)
-inline std::atomic<long long> g_wdiag[8];
-#define W_DIAG_ADD(i, v) rt::g_wdiag[i].fetch_add((long long)(v), std::memory_order_relaxed)
-#else
-#define W_DIAG_ADD(i, v) ((void)0)
 #endif
 
 #ifndef W_STEP_HOOK
@@ -650,8 +610,7 @@ RT_HD double wbvh_child_reach(const WNode& N, int j, const WBoundCtx& C, float Q
     const float rho = wq_len(N.ext2[j] & 0xffu);
     if (!(wr.E < INFINITY) || !(Rlat < INFINITY) || !(Rpar < INFINITY) || !(rho < INFINITY))
         return -1.0;
-    const double rs = fmax(1.0, (double)W_R_SCALE);
-    return fmax(rs * ((double)Rlat + (double)Rpar * (1.0 + 0x1p-16)), 2.0 * (double)rho + (double)C.smax);
+    return fmax((double)Rlat + (double)Rpar * (1.0 + 0x1p-16), 2.0 * (double)rho + (double)C.smax);
 }
 
 inline WSceneBound wbvh_scene_bound(const WNode& root, const float cam[3], const float* light, float S, float QS,
@@ -1345,7 +1304,6 @@ RT_HD int wbvh_closest(const WNode* nodes, const GTri* tris, v3 o, v3 d, float m
 {
     static_assert(G == 1 || ((G & (G - 1)) == 0 && G <= 8 && (Stack::CAP & (Stack::CAP - 1)) == 0),
                   "a lane group: a power of two up to 8 lanes, a ring stack of 2^k entries");
-    static_assert(G == 1 || !W_STEP_CAP, "a lane group leaves the loop together");
     // Feed::on (device, one lane per query): lane refill.  The wave stays in the loop; a lane whose query
     // ended waits, and when at least feed->threshold lanes (or every lane) wait, each hands its query's
     // status and record to feed->finish and takes the next ray from feed->fetch (o, d, m and nob; hi, ties,
@@ -1353,7 +1311,7 @@ RT_HD int wbvh_closest(const WNode* nodes, const GTri* tris, v3 o, v3 d, float m
     // one-query
     // call's: the same state, reset per query, the same steps.  Returns W_MISS once the feed is drained.
     constexpr bool FEED = Feed::on;
-    static_assert(!FEED || (G == 1 && !W_STEP_CAP), "lane refill: one lane per query");
+    static_assert(!FEED || G == 1, "lane refill: one lane per query");
     // the stack index of entry i (a ring in a lane group)
     auto slot = [](int i) { return G > 1 ? (i & (Stack::CAP - 1)) : i; };
     h.t = INFINITY;
@@ -1450,26 +1408,13 @@ RT_HD int wbvh_closest(const WNode* nodes, const GTri* tris, v3 o, v3 d, float m
         ++steps;
         if (max_steps && steps > max_steps)
             return W_LONG;
-#if W_STEP_CAP
-        if (steps > W_STEP_CAP) {   // a very long query: the exact octree walk instead
-            nanhit = true;
-            break;
-        }
-#endif
         // ---- inner nodes: test the four child boxes, go to the nearest, push the others ----
         // if-if: every lane takes one step (inner node or leaf) per iteration
         if (!(cur & W_LEAF)) {
             nn++;
-            W_DIAG_ADD(0, 1);
             W_STEP_HOOK(cur, 0);
             const uint4* p = reinterpret_cast<const uint4*>(nodes + cur);
-#if W_LAZY_EXT2
-            // every row but the last (ext2: rho, read by case (b) alone, per lane when it runs)
-            constexpr int NR = WN_EXT2 / 4;
-            static_assert(WN_EXT2 % 4 == 0 && NR == WN_ROWS - 1, "ext2 is the node's last row");
-#else
             constexpr int NR = WN_ROWS;
-#endif
             uint4 Rw[NR];
 #pragma unroll
             for (int i = 0; i < NR; i++)
@@ -1525,18 +1470,14 @@ RT_HD int wbvh_closest(const WNode* nodes, const GTri* tris, v3 o, v3 d, float m
             }
             float key[W_WIDTH];
             uint32_t ref[W_WIDTH];
-#if W_PRIO_ORDER
             float pri[W_WIDTH];   // visiting order (key: the cull bound kept on the stack)
-#endif
 #pragma unroll
             for (int j = 0; j < W_WIDTH; j++) {
                 const int sh = 8 * (j & 3), jw = j >> 2;
                 const uint32_t chj = wd(WN_CHILD + j);
                 ref[j] = chj;
                 key[j] = INFINITY;
-#if W_PRIO_ORDER
                 pri[j] = INFINITY;
-#endif
                 const uint32_t nrj = wd(WN_NRM + j);
                 const float nx = (float)(int8_t)(nrj & 0xffu), ny = (float)(int8_t)((nrj >> 8) & 0xffu),
                             nz = (float)(int8_t)((nrj >> 16) & 0xffu);
@@ -1553,23 +1494,18 @@ RT_HD int wbvh_closest(const WNode* nodes, const GTri* tris, v3 o, v3 d, float m
                     const float qnx = (float)((nwx[jw] >> sh) & 0xffu), qfx = (float)((fwx[jw] >> sh) & 0xffu);
                     const float qny = (float)((nwy[jw] >> sh) & 0xffu), qfy = (float)((fwy[jw] >> sh) & 0xffu);
                     const float qnz = (float)((nwz[jw] >> sh) & 0xffu), qfz = (float)((fwz[jw] >> sh) & 0xffu);
-                    // D for case (b) (and (a), W_A_CHILD_D): o to the farthest corner of child j's box (it holds the child's
+                    // D for case (b): o to the farthest corner of child j's box (it holds the child's
                     // vertices; Dn's frame can be several times larger, and near the origin (b) is priced
-                    // by D sin(theta))
+                    // by D sin(theta)).  Case (a) keeps the node frame's Dn (sound either way)
                     auto dchild = [&]() -> float {
-#if W_B_CHILD_D
                         const float fx = fmaxf(fabsf(__builtin_fmaf(qnx, stx, Dx)), fabsf(__builtin_fmaf(qfx, stx, Dx)));
                         const float fy = fmaxf(fabsf(__builtin_fmaf(qny, sty, Dy)), fabsf(__builtin_fmaf(qfy, sty, Dy)));
                         const float fz = fmaxf(fabsf(__builtin_fmaf(qnz, stz, Dz)), fabsf(__builtin_fmaf(qfz, stz, Dz)));
                         return fast_sqrt(fx * fx + fy * fy + fz * fz) * (1.0f + 0x1p-16f) + m;
-#else
-                        return Dn;
-#endif
                     };
                     // (a): the box widened by R, the slab by eta + R sin(theta) (wq_reach: the correlated bound of
                     // Moller-Trumbore's reports, D = Dn)
-#if W_SOUND_A
-                    const float Da = W_A_CHILD_D ? dchild() : Dn;
+                    const float Da = Dn;
                     // (a well-conditioned child seen at cos >= W_FAST_Q: the bounds' closed form, wq_fast)
                     const bool fastr = wq_fast_ok(qlb, e);
                     WReach wr;
@@ -1583,12 +1519,9 @@ RT_HD int wbvh_closest(const WNode* nodes, const GTri* tris, v3 o, v3 d, float m
                         E = wr.E;
                         wq_split(wr, L, Da, Rlat, Rpar);
                     }
-                    const float R = __builtin_fmaf(W_R_SCALE, E, m);
-                    const float Rb = __builtin_fmaf(W_R_SCALE, Rlat, m);
-                    const float dtp = W_R_SCALE * Rpar * idl;
-#else
-                    const float R = m, Rb = m, dtp = 0.0f;   // (timing only)
-#endif
+                    const float R = E + m;
+                    const float Rb = Rlat + m;
+                    const float dtp = Rpar * idl;
                     // the entry / exit planes' t of this child's box widened by M:
                     // q (s / d) + (origin - o) / d -+ M / |d| per axis
                     auto box = [&](float M, float& tmin, float& tmax) {
@@ -1616,11 +1549,7 @@ RT_HD int wbvh_closest(const WNode* nodes, const GTri* tris, v3 o, v3 d, float m
                     if (ok && R < INFINITY) {
                         // N . (o + t d - origin) in [C0, C1] widened by w: t between
                         // (C0 - w + b) / a and (C1 + w + b) / a
-#if W_SOUND_A
                         const float eta = fastr ? wq_fast_eta(L, Da) : wq_eta(wr, L, Da);
-#else
-                        const float eta = 0.0f;
-#endif
                         const float w = NLH * __builtin_fmaf(R, sth, eta) * (1.0f + 0x1p-16f) + 384.0f * m;
                         // the hardware reciprocal (1 ulp): its error moves the slab's t by a relative
                         // 2^-23, a distance far inside the margin over the scene
@@ -1632,49 +1561,19 @@ RT_HD int wbvh_closest(const WNode* nodes, const GTri* tris, v3 o, v3 d, float m
                     }
                     if (ok)
                         key[j] = fminf(fmaxf(tmin, 0.0f), 3.0e38f);
-#if defined(W_TRACE) && !defined(__HIP_DEVICE_COMPILE__)
-                    {
-                        // the r03 test (box and slab widened by m only) for comparison: why the child is entered
-                        float t0, t1;
-                        box(m, t0, t1);
-                        bool ok0 = fmaxf(t0, 0.0f) <= fminf(__builtin_fmaf(fabsf(t1), SL, t1), best_s);
-                        bool okbox = ok0;
-                        if (ok0) {
-                            const float ia = fast_rcp(a);
-                            const float s0 = (C0 - 384.0f * m + b) * ia, s1 = (C1 + 384.0f * m + b) * ia;
-                            t0 = fmaxf(t0, fminf(s0, s1));
-                            t1 = fminf(t1, fmaxf(s0, s1));
-                            ok0 = fmaxf(t0, 0.0f) <= fminf(__builtin_fmaf(fabsf(t1), SL, t1), best_s);
-                        }
-                        float b0, b1;
-                        box(Rb, b0, b1);
-                        const bool okRbox = fmaxf(b0 - dtp, 0.0f) <= fminf(b1 + dtp, best_s);
-                        printf("node %u child %d leaf %d: qlb %.4g smin %.3g sth %.3g L %.3g Dn %.3g R %.3g Rlat %.3g Rpar %.3g "
-                               "tmin %.5g tmax %.5g ok %d (tight box %d, tight %d, widened box %d) best %.5g\n",
-                               cur, j, (int)((chj & W_LEAF) != 0), qlb, smin, sth, L, Dn, R, Rlat, Rpar, tmin, tmax, (int)ok,
-                               (int)okbox, (int)ok0, (int)okRbox, best_s);
-                    }
-#endif
-                    W_DIAG_ADD(1, 1);
-                    W_DIAG_ADD(2, ok);
                     // (b): triangles that may lie nearly parallel to d (q < QS), none of whose reports
                     // precedes kbl (the risk key): the line must cross the octree leaves holding them
                     // (the child box widened by rho, any t), and the origin must lie within H0
                     // (wq_h0) of a triangle's plane, so within H0 + D sin(theta)
-                    // of the child's slab (D = Dn >= |o - a|)
+                    // of the child's slab (D = dchild() >= |o - a|)
                     const float rkj = bitsf(rw[2 * j + 1] & 0xFFFF0000u);   // wrisk_key
                     const float kbl = (rkj - rsub) * iqd;
-                    if (W_CASE_B && !risk && !nob && qlb < QS) {
+                    if (!risk && !nob && qlb < QS) {
                         // no risk words (reflection rays, rt_trace_ray):
-                        W_DIAG_ADD(4, 1);
                         // the child box widened by m + rho (any t) and the origin within H0 + D sin(theta) of
                         // the slab; keyed 0 (no risk key bounds the reports' t)
                         float umin, umax;
-#if W_LAZY_EXT2
-                        const uint32_t e2 = ldg(reinterpret_cast<const uint32_t*>(nodes + cur) + WN_EXT2 + j);
-#else
                         const uint32_t e2 = wd(WN_EXT2 + j);
-#endif
                         box(m + wq_len(e2 & 0xffu), umin, umax);
                         bool okb = !(umin > __builtin_fmaf(fabsf(umax), SL, umax));
                         if (okb) {
@@ -1683,20 +1582,11 @@ RT_HD int wbvh_closest(const WNode* nodes, const GTri* tris, v3 o, v3 d, float m
                             const float H0 = wq_h0(QS, L, Dc, smin, s2);
                             const float w = NLH * (H0 + __builtin_fmaf(Dc, sth, m)) * (1.0f + 0x1p-16f) + 384.0f * m;
                             okb = !(-b < C0 - w || -b > C1 + w);
-#if defined(W_TRACE) && !defined(__HIP_DEVICE_COMPILE__)
-                            printf("  (b0) node %u child %d: umin %.4g umax %.4g -b %.4g slab [%.4g, %.4g] w %.4g H0 %.3g Dc %.3g sth %.3g okb %d\n",
-                                   cur, j, umin, umax, -b, C0, C1, w, H0, Dc, sth, (int)okb);
-#endif
                         }
                         if (okb)
                             key[j] = 0.0f;
-                    } else if (W_CASE_B && risk && !nob && qlb < QS && rkj < INFINITY && !(kbl > best_s)) {
-                        W_DIAG_ADD(4, 1);
-#if W_LAZY_EXT2
-                        const uint32_t e2 = ldg(reinterpret_cast<const uint32_t*>(nodes + cur) + WN_EXT2 + j);
-#else
+                    } else if (risk && !nob && qlb < QS && rkj < INFINITY && !(kbl > best_s)) {
                         const uint32_t e2 = wd(WN_EXT2 + j);
-#endif
                         // the at-risk octree leaves' box widened by m + rho (any t)
                         const float Mb = m + wq_len(e2 & 0xffu);
                         const uint32_t r0 = rw[2 * j], r1 = rw[2 * j + 1];   // lo x y z, hi x y z bytes
@@ -1712,23 +1602,14 @@ RT_HD int wbvh_closest(const WNode* nodes, const GTri* tris, v3 o, v3 d, float m
                         bool okb = !(umin > __builtin_fmaf(fabsf(umax), SL, umax));
                         if (okb) {
                             const float s2 = wq_val_nz((e >> 8) & 0xffu, WQ_UNIT);
-                            const float Dc = W_B_CHILD_D >= 2 ? dchild() : Dn;
+                            const float Dc = dchild();
                             const float H0 = wq_h0(QS, L, Dc, smin, s2);
                             const float w = NLH * (H0 + __builtin_fmaf(Dc, sth, m)) * (1.0f + 0x1p-16f) + 384.0f * m;
                             okb = !(-b < C0 - w || -b > C1 + w);   // N . (o - origin) = -b
                         }
-#if defined(W_TRACE) && !defined(__HIP_DEVICE_COMPILE__)
-                        printf("  (b) node %u child %d: okb %d kbl %.5g key %.5g\n", cur, j, (int)okb, kbl, key[j]);
-#endif
-                        if (okb) {
-                            W_DIAG_ADD(3, !ok);
-                            W_DIAG_ADD(6, !ok && (chj & W_LEAF));
-                            W_DIAG_ADD(7, !ok && kbl > 0.0f);
-                            W_DIAG_ADD(5, ok && kbl < key[j]);
+                        if (okb)
                             key[j] = fminf(key[j], fminf(fmaxf(kbl, 0.0f), 3.0e38f));
-                        }
                     }
-#if W_PRIO_ORDER
                     // visit order: the entry t of the child's unwidened box (not below the key).  A child
                     // holding ill-conditioned triangles (UV-sphere pole slivers) has a box widened by a
                     // large R whose entry t precedes the actual hit; ordered by that key the query walked
@@ -1737,31 +1618,20 @@ RT_HD int wbvh_closest(const WNode* nodes, const GTri* tris, v3 o, v3 d, float m
                     if (key[j] < INFINITY)
                         pri[j] = fmaxf(key[j], fmaxf(fmaxf(__builtin_fmaf(qnx, sx, bx), __builtin_fmaf(qny, sy, by)),
                                                      __builtin_fmaf(qnz, sz, bz)));
-#endif
                 }
 #if defined(__HIP_DEVICE_COMPILE__)
                 // one child at a time: the scheduler would interleave the children's
-                // temporaries (VALU latency is hidden by the other waves anyway); a lane group
-                // (the few long queries of split tiles, W_GROUP_ILP) may interleave them
-                if (G == 1 || !W_GROUP_ILP)
-                    __builtin_amdgcn_sched_barrier(0);
+                // temporaries (VALU latency is hidden by the other waves anyway)
+                __builtin_amdgcn_sched_barrier(0);
 #endif
             }
-            // sort the (key, ref) pairs ascending: misses (INFINITY) go last
-#if W_PRIO_ORDER
+            // sort the (pri, key, ref) triples ascending by pri: misses (INFINITY) go last
 #define W_CSWAP(a, b)                                                              \
     if (pri[b] < pri[a]) {                                                         \
         float tp = pri[a]; pri[a] = pri[b]; pri[b] = tp;                           \
         float tk = key[a]; key[a] = key[b]; key[b] = tk;                           \
         uint32_t tr = ref[a]; ref[a] = ref[b]; ref[b] = tr;                        \
     }
-#else
-#define W_CSWAP(a, b)                                                              \
-    if (key[b] < key[a]) {                                                         \
-        float tk = key[a]; key[a] = key[b]; key[b] = tk;                           \
-        uint32_t tr = ref[a]; ref[a] = ref[b]; ref[b] = tr;                        \
-    }
-#endif
             W_CSWAP(0, 1) W_CSWAP(2, 3) W_CSWAP(0, 2) W_CSWAP(1, 3) W_CSWAP(1, 2)
 #undef W_CSWAP
             if (key[0] < INFINITY) {
