@@ -458,6 +458,13 @@ int rt_band_counters(rt_renderer *r, int64_t *shadow_rays, int64_t *reflection_r
  * tree cut it was computed from.  words may be NULL (info only); cap: its size in words.  RT_ESTATE before
  * the first frame launch */
 int rt_tile_mask(rt_renderer *r, int32_t src, uint32_t *words, int64_t cap, int32_t info[5]);
+/* the entry sets of the last frame launch (with its tile mask; RT_TILE_START=0: none): per 8 x 8 block of the
+ * internal image, row-major, the four wide-BVH node links its camera rays' queries start at instead of the
+ * root (0xFFFFFFFF in unused slots; {0, ...}: the root).  src 0: as the device computed them; 1: recomputed on
+ * the host from the same nodes and mask.  info: blocks per row, block rows, 1 when the launch used entry sets
+ * (0: every set is the root's).  sets may be NULL (info only); cap: its size in words (4 per block).
+ * RT_ESTATE before the first frame launch */
+int rt_tile_starts(rt_renderer *r, int32_t src, uint32_t *sets, int64_t cap, int32_t info[3]);
 
 /* ---- tp2/src/mat.cpp restated (host) ---- */
 /* kind: 0 Translation(x,y,z) 1 RotationX(x deg) 2 RotationY 3 RotationZ 4 Scale(x,y,z) 5 Identity */

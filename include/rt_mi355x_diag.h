@@ -77,11 +77,25 @@ int rt_wbvh_query(const float *tri9, int64_t n, int32_t max_depth, int32_t leaf_
  * wide-node visits (the retry's included).  ocone_dim > 0: the origin cones at that
  * resolution for the rays that read no risk words (the reflection queries' skip of case (b));
  * oc_stats[5] (optional) = {cells computed, cells with no triangle at risk, cells without a bound,
- * rays that skipped case (b), grid build ms}. */
+ * rays that skipped case (b), grid build ms}.
+ * entry (optional; cam required, no shadow rays): each camera ray starts at the entry set of its pixel's
+ * 8 x 8 block (wbvh.hpp wbvh_entry_block with the policy k / fan / depth, 0: the
+ * renderer's) instead of the root; a camera without a mask (rt_tile_mask) leaves every ray at the root. */
+typedef struct rt_entry_probe {
+    float proj_inv[16], cam_to_world[16]; /* the camera's matrices (rt_set_camera's) */
+    int32_t rw, rh;                       /* the internal image */
+    int32_t k, fan, depth;                /* the search's policy */
+    int32_t quick;                        /* 1: the quick tree (rt_wbvh_query_ex builds the SAH tree otherwise) */
+    const int32_t *pixel;                 /* [nrays][2]: each ray's pixel (x, y) */
+    uint32_t *sets;                       /* optional, [block rows][blocks per row][4]: the entry sets */
+    int64_t info[4];                      /* out: blocks per row, block rows, 1 when the camera has a mask, covered blocks */
+    int64_t depth_hist[16];               /* out: the links other than the root, by their node's depth (15: deeper) */
+} rt_entry_probe;
 int rt_wbvh_query_ex(const float *tri9, int64_t n, int32_t max_depth, int32_t leaf_max_obj_count, const float *orig,
                      const float *dir, int64_t nrays, const float *cam, const float *light, int32_t shadow_rays,
                      float *o_out, float *d_out, int32_t *status, int32_t *id, float *t, float *u, float *v,
-                     int64_t stats[8], float *ms, int32_t *ray_nodes, int32_t ocone_dim, int64_t oc_stats[5]);
+                     int64_t stats[8], float *ms, int32_t *ray_nodes, int32_t ocone_dim, int64_t oc_stats[5],
+                     rt_entry_probe *entry);
 
 /* The origin cones' soundness by brute force (CPU tests): builds the octree, the wide
  * BVH and the origin-cone grid (ocone_dim cells along the longest axis) over tri9; for each ray whose

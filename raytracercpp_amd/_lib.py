@@ -70,6 +70,15 @@ class RtStats(C.Structure):
         return {n: conv(n, t) for n, t in self._fields_}
 
 
+class RtEntryProbe(C.Structure):
+    """rt_entry_probe (include/rt_mi355x_diag.h): rt_wbvh_query_ex's camera rays start at their blocks' entry sets."""
+    _fields_ = [
+        ("proj_inv", C.c_float * 16), ("cam_to_world", C.c_float * 16), ("rw", C.c_int32), ("rh", C.c_int32),
+        ("k", C.c_int32), ("fan", C.c_int32), ("depth", C.c_int32), ("quick", C.c_int32),
+        ("pixel", _i32p), ("sets", _u32p), ("info", C.c_int64 * 4), ("depth_hist", C.c_int64 * 16),
+    ]
+
+
 # every exported symbol and its ctypes signature (restype, argtypes); tests check
 # that the .so exports exactly what include/rt_mi355x.h declares.
 _H = C.c_void_p
@@ -137,6 +146,7 @@ SIGNATURES = {
     "rt_kernel_times": (C.c_int, [_H, _f32p, C.c_int32]),
     "rt_band_counters": (C.c_int, [_H, _i64p, _i64p]),
     "rt_tile_mask": (C.c_int, [_H, C.c_int32, _u32p, C.c_int64, _i32p]),
+    "rt_tile_starts": (C.c_int, [_H, C.c_int32, _u32p, C.c_int64, _i32p]),
     "rt_make_transform": (None, [C.c_int32, C.c_float, C.c_float, C.c_float, _f32p]),
     "rt_compose": (None, [_f32p, _f32p, _f32p]),
     "rt_inverse": (None, [_f32p, _f32p]),
@@ -162,7 +172,7 @@ SIGNATURES = {
                                 _f32p, _f32p, _i64p, _f32p]),
     "rt_wbvh_query_ex": (C.c_int, [_f32p, C.c_int64, C.c_int32, C.c_int32, _f32p, _f32p, C.c_int64, _f32p, _f32p,
                                    C.c_int32, _f32p, _f32p, _i32p, _i32p, _f32p, _f32p, _f32p, _i64p, _f32p, _i32p,
-                                   C.c_int32, _i64p]),
+                                   C.c_int32, _i64p, C.POINTER(RtEntryProbe)]),
     "rt_ocone_check": (C.c_int, [_f32p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _f32p, _f32p, C.c_int64, _i32p,
                                  _i64p, C.POINTER(C.c_uint32), _i32p, _f32p, C.POINTER(C.c_uint32)]),
     "rt_ocone_read": (C.c_int, [_H, C.POINTER(C.c_uint32), C.c_int64, _i32p, _f32p]),
@@ -366,12 +376,15 @@ def load_obj(path, xform, mat_offset=0):
 
 
 def wbvh_query(tri9, orig, dirs, max_depth=12, leaf=40, cam=None, light=None, shadow_rays=False, rays_out=False,
-               ray_nodes=None, ocone_dim=0, oc_stats=None):
+               ray_nodes=None, ocone_dim=0, oc_stats=None, entry=None):
     """rt_wbvh_query(_ex): the wide-BVH certified closest hit on the host (no GPU).  Returns
     (status, id, t, u, v, stats dict, (octree ms, wide-BVH ms)); status 0 certified miss,
     1 certified hit, 2 not certified.  cam / light: the frame's grazing-risk points (rays from cam
     read the camera's bits); shadow_rays: orig / dirs are hit points and normals, traced as
-    is_shadowed's rays towards light.  rays_out: (o, d) of the queried rays are appended."""
+    is_shadowed's rays towards light.  rays_out: (o, d) of the queried rays are appended.
+    entry: dict(proj_inv, cam_to_world, rw, rh, pixel [n, 2][, k, fan, depth, quick]) -- the camera rays start at
+    their blocks' entry sets; it receives 'sets' [block rows, blocks per row, 4], 'has_mask',
+    'covered' and 'depth_hist'."""
     tri9 = f32(tri9).reshape(-1, 9)
     o = f32(orig).reshape(-1, 3)
     d = f32(dirs).reshape(-1, 3)
@@ -385,13 +398,29 @@ def wbvh_query(tri9, orig, dirs, max_depth=12, leaf=40, cam=None, light=None, sh
     do = np.zeros((n, 3), np.float32)
     c = None if cam is None else f32(cam).reshape(3)
     li = None if light is None else f32(light).reshape(3)
+    ep = None
+    if entry is not None:
+        ep = RtEntryProbe()
+        ep.proj_inv[:] = [float(x) for x in f32(entry["proj_inv"]).ravel()]
+        ep.cam_to_world[:] = [float(x) for x in f32(entry["cam_to_world"]).ravel()]
+        ep.rw, ep.rh = int(entry["rw"]), int(entry["rh"])
+        ep.k, ep.fan, ep.depth = (int(entry.get(x, 0)) for x in ("k", "fan", "depth"))
+        ep.quick = int(entry.get("quick", 0))
+        pix = np.ascontiguousarray(entry["pixel"], np.int32).reshape(-1, 2)
+        assert pix.shape[0] == n
+        sets = np.zeros(((ep.rh + 7) // 8, (ep.rw + 7) // 8, 4), np.uint32)
+        ep.pixel = ptr(pix, _i32p)
+        ep.sets = ptr(sets, _u32p)
     check(lib().rt_wbvh_query_ex(ptr(tri9, _f32p), tri9.shape[0], max_depth, leaf, ptr(o, _f32p), ptr(d, _f32p), n,
                                  None if c is None else ptr(c, _f32p), None if li is None else ptr(li, _f32p),
                                  1 if shadow_rays else 0, ptr(oo, _f32p), ptr(do, _f32p),
                                  ptr(st, _i32p), ptr(ids, _i32p), ptr(t, _f32p), ptr(u, _f32p), ptr(v, _f32p),
                                  ptr(stats, _i64p), ptr(ms, _f32p),
                                  None if ray_nodes is None else ptr(ray_nodes, _i32p), int(ocone_dim),
-                                 None if oc_stats is None else ptr(oc_stats, _i64p)), "rt_wbvh_query")
+                                 None if oc_stats is None else ptr(oc_stats, _i64p),
+                                 None if ep is None else C.byref(ep)), "rt_wbvh_query")
+    if ep is not None:
+        entry.update(sets=sets, has_mask=bool(ep.info[2]), covered=int(ep.info[3]), depth_hist=[int(x) for x in ep.depth_hist])
     keys = ("nodes", "leaves", "max_leaf", "depth", "node_visits", "tri_tests", "violations", "sah_x1000")
     out = (st, ids, t, u, v, dict(zip(keys, map(int, stats))), (float(ms[0]), float(ms[1])))
     return out + (oo, do) if rays_out else out

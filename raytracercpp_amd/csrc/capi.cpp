@@ -482,6 +482,10 @@ int rt_tile_mask(rt_renderer* r, int32_t src, uint32_t* words, int64_t cap, int3
 {
     return guarded(R(r), [&] { return info ? R(r)->tile_mask(src, words, cap, info) : RT_EINVAL; });
 }
+int rt_tile_starts(rt_renderer* r, int32_t src, uint32_t* sets, int64_t cap, int32_t info[3])
+{
+    return guarded(R(r), [&] { return info ? R(r)->tile_starts(src, sets, cap, info) : RT_EINVAL; });
+}
 int rt_band_counters(rt_renderer* r, int64_t* shadow_rays, int64_t* reflection_rays)
 {
     return guarded(R(r), [&] {
@@ -1215,16 +1219,17 @@ int rt_wbvh_query(const float* tri9, int64_t n, int32_t max_depth, int32_t leaf_
                   int64_t stats[8], float* ms)
 {
     return rt_wbvh_query_ex(tri9, n, max_depth, leaf_max_obj_count, orig, dir, nrays, nullptr, nullptr, 0, nullptr,
-                            nullptr, status, id, t, u, v, stats, ms, nullptr, 0, nullptr);
+                            nullptr, status, id, t, u, v, stats, ms, nullptr, 0, nullptr, nullptr);
 }
 
 int rt_wbvh_query_ex(const float* tri9, int64_t n, int32_t max_depth, int32_t leaf_max_obj_count, const float* orig,
                      const float* dir, int64_t nrays, const float* cam, const float* light, int32_t shadow_rays,
                      float* o_out, float* d_out, int32_t* status, int32_t* id, float* t, float* u, float* v,
-                     int64_t stats[8], float* ms, int32_t* ray_nodes, int32_t ocone_dim, int64_t oc_stats[5])
+                     int64_t stats[8], float* ms, int32_t* ray_nodes, int32_t ocone_dim, int64_t oc_stats[5],
+                     rt_entry_probe* entry)
 {
     if (n < 0 || (n > 0 && !tri9) || nrays < 0 || (nrays > 0 && (!orig || !dir || !status || !id || !t || !u || !v)) ||
-        (shadow_rays && !light))
+        (shadow_rays && !light) || (entry && (!cam || shadow_rays || (nrays > 0 && !entry->pixel) || entry->rw <= 0 || entry->rh <= 0)))
         return bad("rt_wbvh_query: bad arguments");
     try {
         rt::FlatOctree f;
@@ -1232,7 +1237,10 @@ int rt_wbvh_query_ex(const float* tri9, int64_t n, int32_t max_depth, int32_t le
         auto t0 = std::chrono::steady_clock::now();
         rt::build_flat_octree(tri9, n, max_depth, leaf_max_obj_count, f);
         auto t1 = std::chrono::steady_clock::now();
-        rt::build_wbvh(f, w);
+        if (entry && entry->quick)
+            rt::build_wbvh_quick(f, w);
+        else
+            rt::build_wbvh(f, w);
         if (ms) {
             ms[0] = std::chrono::duration<float, std::milli>(t1 - t0).count();
             ms[1] = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t1).count();
@@ -1303,6 +1311,49 @@ int rt_wbvh_query_ex(const float* tri9, int64_t n, int32_t max_depth, int32_t le
                 ocv.ih = ocg.ih;
             }
         }
+        // the blocks' entry sets (renderer.cpp prepare_mask: the cut, the mask, then the entry search)
+        std::vector<uint32_t> esets;
+        int ebw = 0;
+        if (entry) {
+            int mode;
+            float pw;
+            rt::wbvh_proj_shortcut(entry->proj_inv, mode, pw);
+            const float* c = entry->cam_to_world;
+            const int affine = c[12] == 0.0f && c[13] == 0.0f && c[14] == 0.0f && c[15] == 1.0f;
+            const rt::WMaskCam C = rt::wbvh_mask_cam(entry->proj_inv, c, mode, pw, affine, cam, light, S, W_QS_CLOSEST,
+                                                     entry->rw, entry->rh);
+            entry->info[0] = C.bw;
+            entry->info[1] = C.bh;
+            entry->info[2] = usable && C.valid;
+            entry->info[3] = 0;
+            if (usable && C.valid) {
+                std::vector<uint32_t> cut, words;
+                rt::wbvh_cut_host(w.nodes.data(), (int64_t)w.nodes.size(), W_CUT_BUDGET, W_CUT_DEPTH, W_QS_CLOSEST, cut);
+                rt::wbvh_mask_host(w.nodes.data(), (int64_t)w.nodes.size(), w.parent.data(), cut, C, words);
+                for (uint32_t x : words)
+                    entry->info[3] += __builtin_popcount(x);
+                rt::wbvh_entry_host(w.nodes.data(), (int64_t)w.nodes.size(), C, words.data(), entry->k > 0 ? entry->k : W_ENTRY_K,
+                                    entry->fan > 0 ? entry->fan : W_ENTRY_FAN, entry->depth > 0 ? entry->depth : W_CUT_DEPTH,
+                                    esets);
+                ebw = C.bw;
+            }
+            if (entry->sets) {
+                const size_t nb = (size_t)C.bw * C.bh;
+                for (size_t b = 0; b < nb; b++)
+                    for (int k = 0; k < rt::W_ENTRY_MAX; k++)
+                        entry->sets[b * rt::W_ENTRY_MAX + k] = esets.empty() ? (k ? rt::W_EMPTY : 0u) : esets[b * rt::W_ENTRY_MAX + k];
+            }
+            // the links' depths, over the blocks that do not start at the root
+            for (int k = 0; k < 16; k++)
+                entry->depth_hist[k] = 0;
+            for (uint32_t l : esets)
+                if (l != rt::W_EMPTY && l != 0u) {
+                    int dep = 0;
+                    for (uint32_t x = l; dep < 15 && w.parent[x] != rt::W_EMPTY; x = w.parent[x] >> 2)
+                        dep++;
+                    entry->depth_hist[dep]++;
+                }
+        }
         std::atomic<int64_t> work_n{0}, work_t{0}, n_nob{0};
         const bool probe_hi = std::getenv("RT_WQ_PROBE_HI") != nullptr;
         auto body = [&](int64_t b, int64_t e) {
@@ -1367,9 +1418,16 @@ int rt_wbvh_query_ex(const float* tri9, int64_t n, int32_t max_depth, int32_t le
                     nob = rt::risk_cap_skip(cap[1], cap_dir[1], d, W_QS_SHADOW);
                 if (nob)
                     ++n_nob;
+                // a camera ray's entry set: its pixel's block's (the frame kernel's trace_pixel)
+                const uint32_t* start = nullptr;
+                if (!esets.empty() && rk) {
+                    const int px = entry->pixel[2 * i], py = entry->pixel[2 * i + 1];
+                    if (px >= 0 && py >= 0 && px < entry->rw && py < entry->rh)
+                        start = &esets[((size_t)(py >> 3) * ebw + (px >> 3)) * rt::W_ENTRY_MAX];
+                }
                 int st = rt::wbvh_closest(w.nodes.data(), w.tris.data(), o, d, m, stk, h, wk, INFINITY, true,
                                           shadow_rays ? W_QS_SHADOW : W_QS_CLOSEST, rk, rsel, rsub, 0u,
-                                          (rt::WNoFeed*)nullptr, nob);
+                                          (rt::WNoFeed*)nullptr, nob, start);
                 if (st == rt::W_DEEP) {   // the kernels' retry with a deeper stack (kernels.hip wide_closest_deep)
                     rt::WStackArr<rt::W_DEEP_STACK> deep;
                     st = rt::wbvh_closest(w.nodes.data(), w.tris.data(), o, d, m, deep, h, wk, INFINITY, true,

@@ -964,7 +964,8 @@ __device__ __forceinline__ float wide_margin(const KParams& P, v3 o)
 // is not counted)
 template <class Stk, int G>
 __device__ __forceinline__ int wide_run(const KParams& P, v3 o, v3 d, uint2* lv, WHit& w, float hi, bool ties, float QS,
-                                        const uint64_t* rk, int rsel, float rsub, uint32_t max_steps, bool nob, int count)
+                                        const uint64_t* rk, int rsel, float rsub, uint32_t max_steps, bool nob, int count,
+                                        const uint32_t* start = nullptr)
 {
     const float m = wide_margin(P, o);
     Stk stk{lv};
@@ -975,7 +976,7 @@ __device__ __forceinline__ int wide_run(const KParams& P, v3 o, v3 d, uint2* lv,
     uint32_t* wk = nullptr;
 #endif
     int st = wbvh_closest<Stk, G>(P.wnodes, P.wtris, o, d, m, stk, w, wk, hi, ties, QS, rk, rsel, rsub, max_steps,
-                                  (WNoFeed*)nullptr, nob);
+                                  (WNoFeed*)nullptr, nob, start);
 #if RT_COUNT
     if (wk) {
         count_wave_steps(P, count, wk[3]);
@@ -1010,9 +1011,13 @@ __device__ __forceinline__ bool wide_certified(const KParams& P, const WHit& w, 
 // certified; false when it must be traced through the octree.
 // rec (optional): on a certified hit, the record built from the wide BVH's own copies (the
 // triangle from wtris, index and material from wmeta), with no further dependent loads.
-template <int G = 1, int CAP = W_STACK>
+// START (the plain frame kernel's camera rays): the query starts at the entry set of the pixel's 8 x 8 block
+// (KParams::tile_start[bidx], wbvh.hpp wbvh_entry_block; bidx < 0: at the root).  The set is
+// loaded here, after everything the tile loop computes, and goes straight to the lane's LDS stack.  The
+// deeper-stack retry (wide_closest_deep) keeps the root.
+template <int G = 1, int CAP = W_STACK, bool START = false>
 __device__ __forceinline__ bool wide_closest(const KParams& P, v3 o, v3 d, THit& h, bool& r, uint2* lv,
-                                             Rec* rec = nullptr, uint32_t max_steps = 0, bool* longq = nullptr)
+                                             Rec* rec = nullptr, uint32_t max_steps = 0, bool* longq = nullptr, int bidx = -1)
 {
     using Stk = WStackLdsN<G == 1 ? CAP : W_STACK>;   // (a lane group's ring: W_STACK entries)
     WHit w;
@@ -1025,8 +1030,17 @@ __device__ __forceinline__ bool wide_closest(const KParams& P, v3 o, v3 d, THit&
     // no child entered (wbvh.hpp wbvh_scene_bound); a wave whose lanes all miss it runs no step at all
     int st = W_MISS;
     // (RT_COUNT builds pass no step limit, deliberately: they defer no query and count each to its end)
-    if (!(cam && P.sb_valid && scene_bound_rejects(P.sb_lo, P.sb_hi, o, d)))
-        st = wide_run<Stk, G>(P, o, d, lv, w, INFINITY, true, W_QS_CLOSEST, rk, 0, 0.0f, RT_COUNT ? 0u : max_steps, nob, 22);
+    if (!(cam && P.sb_valid && scene_bound_rejects(P.sb_lo, P.sb_hi, o, d))) {
+        if constexpr (START) {
+            uint32_t s[W_ENTRY_MAX] = {0u, W_EMPTY, W_EMPTY, W_EMPTY};
+            if (bidx >= 0 && cam) {
+                const uint4 e = ldg(P.tile_start + bidx);
+                s[0] = e.x; s[1] = e.y; s[2] = e.z; s[3] = e.w;
+            }
+            st = wide_run<Stk, G>(P, o, d, lv, w, INFINITY, true, W_QS_CLOSEST, rk, 0, 0.0f, RT_COUNT ? 0u : max_steps, nob, 22, s);
+        } else
+            st = wide_run<Stk, G>(P, o, d, lv, w, INFINITY, true, W_QS_CLOSEST, rk, 0, 0.0f, RT_COUNT ? 0u : max_steps, nob, 22);
+    }
     if (max_steps && st == W_LONG) {   // (only a query with a step limit comes back long)
         *longq = true;
         return false;
@@ -1289,7 +1303,7 @@ __device__ __forceinline__ void shapes_closest(const KParams& P, v3 o, v3 d, Rec
 // With the wide BVH (P.wnodes), a certified query takes its answer; one it cannot certify
 // is traced through the octree here.
 template <bool PLAIN = false, int G = 1, bool OCT = false>
-__device__ int closest_hit(const KParams& P, v3 o, v3 d, Rec& fin, uint2* lv)
+__device__ int closest_hit(const KParams& P, v3 o, v3 d, Rec& fin, uint2* lv, int bidx = -1)
 {
     Rec local = rec_fresh();
     int src = -1;
@@ -1297,7 +1311,8 @@ __device__ int closest_hit(const KParams& P, v3 o, v3 d, Rec& fin, uint2* lv)
         THit h;
         bool r = false;
         const bool wide = !OCT && P.wnodes && P.nnodes > 0 && !ray_is_nan(o, d);
-        if (wide && wide_closest<G, PLAIN ? W_STACK_PLAIN : W_STACK>(P, o, d, h, r, lv, &local)) {
+        // (bidx: the camera ray's block, KParams::tile_start; the plain kernel's primary queries only)
+        if (wide && wide_closest<G, PLAIN ? W_STACK_PLAIN : W_STACK, PLAIN && !OCT>(P, o, d, h, r, lv, &local, 0u, nullptr, bidx)) {
             // certified: a hit's record is already in local (a miss leaves it fresh)
             if (r && (local.t < fin.t || fin.t == -1)) {
                 fin = local;
@@ -1549,13 +1564,13 @@ struct PixelOut {
 // compute_reflection recursion (when REFL) unrolled onto an explicit stack.
 template <bool REFL, bool PLAIN = false, int G = 1, bool OCT = false>
 __device__ PixelOut trace_pixel(const KParams& P, v3 cam, v3 rd0, uint2* lv, uint32_t pixel_key, unsigned& nshadow,
-                                unsigned& nrefl)
+                                unsigned& nrefl, int bidx = -1)
 {
     PixelOut po;
     po.fin = rec_fresh();
     po.found = po.shadowed = false;
     po.alpha = 1.0f;
-    po.src = closest_hit<PLAIN && !REFL, REFL ? 1 : G, OCT>(P, cam, rd0, po.fin, lv);
+    po.src = closest_hit<PLAIN && !REFL, REFL ? 1 : G, OCT>(P, cam, rd0, po.fin, lv, bidx);
     if (PLAIN) PH_MARK(2);
     if (!REFL) {
         if (PLAIN && po.fin.t > 0.1f) {
@@ -2001,6 +2016,12 @@ __device__ __forceinline__ v3 camera_dir(const KParams& P, int px, int py, v3 ca
 // different waves at the same time; each adds its cycles to the tile's cost (heavy_prep_kernel zeroed
 // it).  Plain scenes over the wide BVH only, fused SSAA factors up to 8 / G (the host checks).  Per
 // pixel the results are trace_pixel<false, true>'s: the group's query returns the one-lane answer.
+// the entry set of pixel (px, py)'s block in KParams::tile_start (-1: none; the launch has no entry sets)
+__device__ __forceinline__ int tile_start_index(const KParams& P, int px, int py)
+{
+    return P.tile_start ? (py >> 3) * P.start_bw + (px >> 3) : -1;
+}
+
 template <int G>
 __device__ __forceinline__ void trace_split_part(const KParams& P, uint2* lv, int t, int lane, unsigned& nshadow)
 {
@@ -2025,7 +2046,7 @@ __device__ __forceinline__ void trace_split_part(const KParams& P, uint2* lv, in
         const v3 cam = mk(P.cam_pos[0], P.cam_pos[1], P.cam_pos[2]);
         const v3 rd = camera_dir(P, px, py, cam);
         unsigned ns = 0, nr = 0;
-        PixelOut po = trace_pixel<false, true, G>(P, cam, rd, lv, 0u, ns, nr);
+        PixelOut po = trace_pixel<false, true, G>(P, cam, rd, lv, 0u, ns, nr, tile_start_index(P, px, py));
         if ((lane & (G - 1)) == 0)
             nshadow += ns;   // (one count per pixel)
         const size_t o = (size_t)lr * P.rw + px;
@@ -2166,7 +2187,8 @@ __global__ __launch_bounds__(BLOCK, OCT ? RT_OCC_OCT : PLAIN ? RT_OCC_PLAIN : RT
         if (PLAIN) PH_MARK(1);
 
         uint32_t rng = REFL ? pixel_seed((uint32_t)(py * P.rw + px), P.rng_seed) : 0u;
-        PixelOut po = trace_pixel<REFL, PLAIN, 1, OCT>(P, cam, rd, lv, rng, nshadow, nrefl);
+        PixelOut po = trace_pixel<REFL, PLAIN, 1, OCT>(P, cam, rd, lv, rng, nshadow, nrefl,
+                                                        PLAIN && !REFL && !OCT ? tile_start_index(P, px, py) : -1);
         size_t o = (size_t)lr * P.rw + px;
         if (P.argb) P.argb[o] = color_to_argb(po.color);
         if (!REFL && P.ds_out) downscale_tile(P, lane, lr, px, color_to_argb(po.color));
@@ -4009,6 +4031,35 @@ __global__ __launch_bounds__(256) void wide_mask_kernel(const rt::WNode* __restr
             if ((__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & m) != m)
                 atomicOr(p, m);
         }
+}
+
+// The entry sets of one camera (wbvh.hpp wbvh_entry_host): one thread per 8 x 8 block of the mask's grid; a
+// block whose mask bit is clear keeps the root
+__global__ __launch_bounds__(256) void wide_entry_kernel(const rt::WNode* __restrict__ nodes, int nnodes, rt::WMaskCam C,
+                                                         const uint32_t* __restrict__ words, int K, int fan, int max_depth,
+                                                         uint4* out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= (uint32_t)(C.bw * C.bh))
+        return;
+    const int bx = (int)(i % (uint32_t)C.bw), by = (int)(i / (uint32_t)C.bw);
+    uint4 r = make_uint4(0u, rt::W_EMPTY, rt::W_EMPTY, rt::W_EMPTY);
+    if ((words[(size_t)by * C.wpr + (bx >> 5)] >> (bx & 31)) & 1u) {
+        const rt::WEntrySet S = rt::wbvh_entry_block(nodes, nnodes, C, bx, by, K, fan, max_depth);
+        r = make_uint4(S.link[0], S.link[1], S.link[2], S.link[3]);
+    }
+    out[i] = r;
+}
+
+hipError_t rt_launch_wide_entry(const rt::WNode* wnodes, int nnodes, const rt::WMaskCam* C, const uint32_t* words, int K,
+                                int fan, int max_depth, uint4* out, hipStream_t stream)
+{
+    const int nb = C->bw * C->bh;
+    if (nb <= 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(wide_entry_kernel, dim3((nb + 255) / 256), dim3(256), 0, stream, wnodes, nnodes, *C, words, K, fan,
+                       max_depth, out);
+    return hipGetLastError();
 }
 
 hipError_t rt_launch_wide_cut(const rt::WNode* wnodes, int nnodes, int budget, int max_depth, uint32_t* buf, hipStream_t stream)

@@ -74,6 +74,11 @@ struct KParams {
     // a clear bit: no ray of the block enters the cut through the wide BVH, every pixel is the background's
     const uint32_t* tile_mask;
     int32_t mask_wpr;
+    // the entry sets (wbvh.hpp wbvh_entry_block; with tile_mask; nullptr: none): block (px >> 3,
+    // py >> 3)'s camera rays start their wide query at the nodes tile_start[(py >> 3) start_bw + (px >> 3)]
+    // names (W_EMPTY in unused slots; {0, ...}: the root)
+    const uint4* tile_start;
+    int32_t start_bw;
     // the origin cones (ocone.hpp; cells nullptr: none resident): the rays without risk words whose
     // ocone_skip holds skip case (b) (the reflection queries, ReflFeed)
     OConeView ocone;

@@ -62,6 +62,10 @@ RT_LAUNCH rt_launch_wide_risk(const rt::GTri* wtris, const uint4* wmeta, const r
 RT_LAUNCH rt_launch_wide_cut(const rt::WNode* wnodes, int nnodes, int budget, int max_depth, uint32_t* buf, hipStream_t stream);
 RT_LAUNCH rt_launch_wide_mask(const rt::WNode* wnodes, int nnodes, const uint32_t* parent, const uint32_t* cut, int budget,
                               const rt::WMaskCam* C, uint32_t* words, hipStream_t stream);
+// the entry sets of the same camera (wbvh.hpp wbvh_entry_block) into out (bh x bw uint4), from
+// the mask's words
+RT_LAUNCH rt_launch_wide_entry(const rt::WNode* wnodes, int nnodes, const rt::WMaskCam* C, const uint32_t* words, int K,
+                               int fan, int max_depth, uint4* out, hipStream_t stream);
 RT_LAUNCH rt_launch_ocone(const rt::OConeEnt* E, const rt::GTri* tris, const uint32_t* todo, int n, const float lo[3],
                           const int32_t dim[3], double h, double r, double slack, double QS, double cos_cap,
                           uint2* cells, size_t ncells, hipStream_t stream);

@@ -127,6 +127,7 @@ Knobs Knobs::from_env()
     k.risk_cap = flag("RT_RISK_CAP", k.risk_cap);
     k.scene_bound = flag("RT_SCENE_BOUND", k.scene_bound);
     k.tile_mask = flag("RT_TILE_MASK", k.tile_mask);
+    k.tile_start = flag("RT_TILE_START", k.tile_start);
     k.cut_budget = std::min((int)W_CUT_MAX, std::max((int)W_WIDTH, num("RT_TILE_MASK_CUT", k.cut_budget)));
     k.ocone = flag("RT_OCONE", k.ocone);
     k.ocone_dim = std::min(1024, std::max(1, num("RT_OCONE_DIM", k.ocone_dim)));
@@ -2705,7 +2706,10 @@ int Renderer::prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M)
 {
     P.tile_mask = nullptr;
     P.mask_wpr = 0;
+    P.tile_start = nullptr;
+    P.start_bw = 0;
     mask_last_ = nullptr;
+    starts_last_ = false;
     mask_seen_ = true;
     if (!knobs_.tile_mask || !P.wnodes || !P.plain || P.has_reflection || P.zbuf || P.nbuf || wide_.nn <= 0 || !wide_.b_links.p ||
         s_.hybrid_rasterization_tracing)
@@ -2737,9 +2741,28 @@ int Renderer::prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M)
             return hip_fail(e, "wide_mask_kernel");
         M.cut_gen = cut_gen_;
         std::memcpy(&M.cam, &C, sizeof C);
+        M.starts_valid = false;
+        M.launches = 0;
+    }
+    M.launches++;
+    // the blocks' entry sets, from the stream's words, on the same stream: at the second launch in a
+    // row with these words.  The search costs more than one frame gains (wide_entry_kernel, profiles/entry_nodes/),
+    // so a camera that moves every launch starts at the root, as before; one at rest pays once
+    if (knobs_.tile_start && !M.starts_valid && M.launches >= 2) {
+        if ((e = M.starts.reserve((size_t)C.bh * C.bw * sizeof(uint4))) != hipSuccess)
+            return hip_fail(e, "hipMalloc (entry sets)");
+        if ((e = rt_launch_wide_entry(P.wnodes, (int)wide_.nn, &C, M.words.as<uint32_t>(), W_ENTRY_K, W_ENTRY_FAN,
+                                      W_CUT_DEPTH, M.starts.as<uint4>(), stream)) != hipSuccess)
+            return hip_fail(e, "wide_entry_kernel");
+        M.starts_valid = true;
     }
     P.tile_mask = M.words.as<uint32_t>();
     P.mask_wpr = C.wpr;
+    if (M.starts_valid) {
+        P.tile_start = M.starts.as<uint4>();
+        P.start_bw = C.bw;
+        starts_last_ = true;
+    }
     mask_last_ = &M;
     return RT_OK;
 }
@@ -3167,6 +3190,51 @@ int Renderer::tile_mask(int src, uint32_t* out, int64_t cap, int32_t info[5])
         if (cut.size() != ncut)
             return fail(RT_ESTATE, "tile_mask: the host's cut differs from the device's in size");
         std::memcpy(out, words.data(), nw * 4);
+    }
+    return RT_OK;
+}
+
+// The last frame launch's entry sets (rt_tile_starts): src 0 as the device computed them, src 1 recomputed on
+// the host from the resident nodes and the device's mask words.  info: blocks per row, block rows, 1 when the
+// launch was given entry sets (0: none; every set is then the root's).
+int Renderer::tile_starts(int src, uint32_t* out, int64_t cap, int32_t info[3])
+{
+    hipSetDevice(device_);
+    if (!mask_seen_)
+        return fail(RT_ESTATE, "tile_starts: no frame launch yet");
+    if (src != 0 && src != 1)
+        return fail(RT_EINVAL, "tile_starts: src is 0 (device) or 1 (host)");
+    int rw, rh;
+    render_size(rw, rh);
+    const bool on = mask_last_ != nullptr && starts_last_;
+    const int bw = mask_last_ ? mask_last_->cam.bw : (rw + 7) / 8, bh = mask_last_ ? mask_last_->cam.bh : (rh + 7) / 8;
+    info[0] = bw;
+    info[1] = bh;
+    info[2] = on ? 1 : 0;
+    const size_t nw = (size_t)bw * bh * W_ENTRY_MAX;
+    if (!out)
+        return RT_OK;
+    if (cap < (int64_t)nw)
+        return fail(RT_EINVAL, "tile_starts: the buffer is too small");
+    if (!on) {
+        for (size_t i = 0; i < nw; i++)
+            out[i] = i % W_ENTRY_MAX ? W_EMPTY : 0u;
+        return RT_OK;
+    }
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess && src == 0)
+        e = hipMemcpy(out, mask_last_->starts.p, nw * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess)
+        return hip_fail(e, "tile_starts");
+    if (src == 1) {
+        const WMaskCam& C = mask_last_->cam;
+        std::vector<WNode> nodes((size_t)wide_.nn);
+        std::vector<uint32_t> words((size_t)C.bh * C.wpr), sets;
+        if ((e = hipMemcpy(nodes.data(), wide_.nodes(), nodes.size() * sizeof(WNode), hipMemcpyDeviceToHost)) != hipSuccess ||
+            (e = hipMemcpy(words.data(), mask_last_->words.p, words.size() * 4, hipMemcpyDeviceToHost)) != hipSuccess)
+            return hip_fail(e, "download (wide BVH nodes, mask words)");
+        wbvh_entry_host(nodes.data(), (int64_t)nodes.size(), C, words.data(), W_ENTRY_K, W_ENTRY_FAN, W_CUT_DEPTH, sets);
+        std::memcpy(out, sets.data(), nw * 4);
     }
     return RT_OK;
 }

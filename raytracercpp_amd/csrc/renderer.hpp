@@ -158,6 +158,8 @@ struct Knobs {
                               // still run their root step, wbvh.hpp wbvh_scene_bound)
     bool tile_mask = true;    // RT_TILE_MASK=0: no tile mask (every background tile generates its rays and runs
                               // the scene bound, wbvh.hpp wbvh_mask_rect)
+    bool tile_start = true;   // RT_TILE_START=0: no entry sets (every camera ray starts its wide query at the root,
+                              // wbvh.hpp wbvh_entry_block); no mask, no entry sets
     int cut_budget = W_CUT_BUDGET;  // RT_TILE_MASK_CUT=n (4 .. 65536): the largest cut the mask is computed from
     bool ocone = true;        // RT_OCONE=0: no origin cones (reflection queries always run case (b), ocone.hpp)
     int ocone_dim = 128;      // RT_OCONE_DIM=n: the origin-cone grid's cells along the scene's longest axis
@@ -267,6 +269,7 @@ public:
     int kernel_times(float* ms, int n);
     int band_counters(unsigned long long out[2]);
     int tile_mask(int src, uint32_t* out, int64_t cap, int32_t info[5]);   // rt_tile_mask
+    int tile_starts(int src, uint32_t* out, int64_t cap, int32_t info[3]); // rt_tile_starts
     int debug_read(uint64_t* out, int64_t n);   // diagnostic builds: the per-wave records of the last frame
     int tile_costs(uint32_t* out, int64_t n, int32_t* tiles_x, int32_t* tiles_y);   // trace_frame's last tile costs
     // the resident origin-cone grid (ocone.hpp; rt_ocone_read): its frame, and its words when out holds them
@@ -511,6 +514,11 @@ private:
     // each other.  mask_last_: the mask the last launch was given (nullptr: none).
     struct MaskSlot {
         DevBuf words;
+        // the blocks' entry sets (bh x bw uint4) from the words, computed at the stream's second
+        // launch in a row with the same camera and cut (a camera that moves every launch never pays for them)
+        DevBuf starts;
+        bool starts_valid = false;
+        uint32_t launches = 0; // the stream's launches in a row with these words
         WMaskCam cam{};        // the camera the words were computed for
         uint64_t cut_gen = 0;  // and the cut (0: no words yet)
     };
@@ -519,6 +527,7 @@ private:
     uint64_t cut_gen_ = 0;
     MaskSlot mask_main_;       // rt_ray_trace's (stream_)
     MaskSlot* mask_last_ = nullptr;
+    bool starts_last_ = false; // the last launch was given entry sets (mask_last_->starts)
     Fence cut_fence_;
     int prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M);
     DevBuf d_dbg_;                          // diagnostic per-wave records (RT_DEBUG_WAVES)

@@ -862,6 +862,24 @@ inline WMaskCam wbvh_mask_cam(const float proj_inv[16], const float c2w[16], int
     return C;
 }
 
+// KParams::proj_mode / proj_w of an inverse projection, as renderer.cpp fill_params derives them (host tools)
+inline void wbvh_proj_shortcut(const float m[16], int& mode, float& w)
+{
+    mode = 0;
+    w = 1.0f;
+    bool fin = true;
+    for (int i = 0; i < 16; i++)
+        fin = fin && std::isfinite(m[i]);
+    if (fin && m[12] == 0.0f && m[13] == 0.0f && m[14] != 0.0f) {
+        volatile float mz = m[14] * -1.0f;   // (volatile: evaluated as the kernel does, in float)
+        const float wt = mz + m[15];
+        if (std::isfinite(wt) && wt != 0.0f) {
+            mode = wt == 1.0f ? 1 : 2;
+            w = 1.0f / wt;
+        }
+    }
+}
+
 // The blocks a cut entry may touch: [x0, x1] x [y0, y1] inclusive (empty: x0 > x1); an entry whose widened
 // box has no projection (a corner on either side of, or near, the camera's plane s = 0; no finite W; a
 // failed gate) covers every block.
@@ -972,6 +990,144 @@ inline void wbvh_mask_host(const WNode* nodes, int64_t nnodes, const uint32_t* p
             for (int w = R.x0 >> 5; w <= R.x1 >> 5; w++)
                 words[(size_t)y * C.wpr + w] |= wbvh_mask_word(R, w);
     }
+}
+
+// ---------------------------------------------------------------------------------
+// Entry nodes: where the camera rays of an 8 x 8 block can go, found once per camera.  A
+// camera ray enters child j of node N only if its pixel lies in wbvh_mask_rect(N, j, C) (5.12), so the rays
+// of block b that reach N go on into c(N) = the non-empty children whose rectangle holds b, and nowhere else.
+// Top-down from the root, a frontier node N is replaced by the child nodes of c(N) while every member of
+// c(N) is an inner node (no triangle is ever tested above the frontier), |c(N)| <= fan, the frontier stays
+// within K nodes and below max_depth; a node with an empty c(N) is dropped.  The block's primary queries
+// start at the frontier's nodes instead of the root (wbvh_closest's start set).  The links are ordered by the
+// distance of the node's frame from the camera, nearest first (the order does not change the answer: the
+// near subtree sets the best hit before the far one is visited); unused slots hold W_EMPTY; an empty result
+// is stored as the root {0, W_EMPTY, ...}.
+constexpr int W_ENTRY_MAX = 4;   // links per block (one uint4)
+#ifndef W_ENTRY_K
+#define W_ENTRY_K 4
+#endif
+#ifndef W_ENTRY_FAN
+#define W_ENTRY_FAN 3   // (tools/visit_probe.py, profiles/entry_nodes/host_probe.log: K 4, fan 3 saves the most)
+#endif
+
+struct WEntrySet {
+    uint32_t link[W_ENTRY_MAX];
+};
+
+RT_HD bool wbvh_rect_holds(const WMaskRect& R, int bx, int by)
+{
+    return bx >= R.x0 && bx <= R.x1 && by >= R.y0 && by <= R.y1;
+}
+
+// squared distance of cam from node N's frame [origin, origin + 255 step] (the links' order)
+RT_HD double wbvh_entry_dist(const WNode& N, const float cam[3])
+{
+    const double org[3] = {N.ox, N.oy, N.oz};
+    double s = 0.0;
+    for (int a = 0; a < 3; a++) {
+        const double st = (double)__builtin_bit_cast(float, ((N.exps >> (8 * a)) & 0xffu) << 23);
+        const double lo = org[a], hi = org[a] + 255.0 * st, c = (double)cam[a];
+        const double g = c < lo ? lo - c : (c > hi ? c - hi : 0.0);
+        s += g * g;
+    }
+    return s == s ? s : INFINITY;
+}
+
+RT_HD WEntrySet wbvh_entry_block(const WNode* nodes, int64_t nnodes, const WMaskCam& C, int bx, int by, int K, int fan,
+                                 int max_depth)
+{
+    WEntrySet S;
+    for (int i = 0; i < W_ENTRY_MAX; i++)
+        S.link[i] = W_EMPTY;
+    S.link[0] = 0u;
+    if (nnodes <= 0 || !C.valid)
+        return S;
+    K = K < 1 ? 1 : (K > W_ENTRY_MAX ? W_ENTRY_MAX : K);
+    uint32_t fn[W_ENTRY_MAX];
+    int fd[W_ENTRY_MAX];
+    bool fin[W_ENTRY_MAX];
+    int n = 1;
+    fn[0] = 0u;
+    fd[0] = 0;
+    fin[0] = false;
+    for (;;) {
+        // the shallowest node still open (the first of them): the budget goes to the levels in turn
+        int i = n;
+        for (int k = 0; k < n; k++)
+            if (!fin[k] && (i == n || fd[k] < fd[i]))
+                i = k;
+        if (i == n)
+            break;
+        const WNode& N = nodes[fn[i]];
+        uint32_t ch[W_WIDTH];
+        int cnt = 0;
+        bool inner = true;
+        for (int j = 0; j < W_WIDTH; j++) {
+            const uint32_t c = N.child[j];
+            if (c == W_EMPTY || !wbvh_rect_holds(wbvh_mask_rect(N, j, C), bx, by))
+                continue;
+            inner = inner && !(c & W_LEAF) && (int64_t)c < nnodes;
+            ch[cnt++] = c;
+        }
+        if (cnt == 0) {   // no ray of the block goes below N
+            for (int k = i + 1; k < n; k++) {
+                fn[k - 1] = fn[k];
+                fd[k - 1] = fd[k];
+                fin[k - 1] = fin[k];
+            }
+            n--;
+            continue;
+        }
+        if (!inner || cnt > fan || n - 1 + cnt > K || fd[i] + 1 >= max_depth) {
+            fin[i] = true;
+            continue;
+        }
+        fn[i] = ch[0];
+        fd[i]++;
+        for (int k = 1; k < cnt; k++) {
+            fn[n] = ch[k];
+            fd[n] = fd[i];
+            fin[n] = false;
+            n++;
+        }
+    }
+    if (n == 0)
+        return S;   // (the root: its query ends after one step)
+    double key[W_ENTRY_MAX];
+    for (int i = 0; i < n; i++)
+        key[i] = wbvh_entry_dist(nodes[fn[i]], C.cam);
+    for (int i = 1; i < n; i++)   // nearest first; equal distances by node index
+        for (int k = i; k > 0 && (key[k] < key[k - 1] || (key[k] == key[k - 1] && fn[k] < fn[k - 1])); k--) {
+            const double tk = key[k];
+            key[k] = key[k - 1];
+            key[k - 1] = tk;
+            const uint32_t tf = fn[k];
+            fn[k] = fn[k - 1];
+            fn[k - 1] = tf;
+        }
+    for (int i = 0; i < n; i++)
+        S.link[i] = fn[i];
+    return S;
+}
+
+// The entry sets on the host (the device's: kernels.hip wide_entry_kernel): W_ENTRY_MAX words per block,
+// row-major over the mask's block grid; a block whose mask bit is clear (words: wbvh_mask_host's; nullptr:
+// every block is covered) keeps the root
+inline void wbvh_entry_host(const WNode* nodes, int64_t nnodes, const WMaskCam& C, const uint32_t* words, int K, int fan,
+                            int max_depth, std::vector<uint32_t>& out)
+{
+    out.assign((size_t)C.bw * C.bh * W_ENTRY_MAX, W_EMPTY);
+    for (int by = 0; by < C.bh; by++)
+        for (int bx = 0; bx < C.bw; bx++) {
+            uint32_t* o = &out[((size_t)by * C.bw + bx) * W_ENTRY_MAX];
+            o[0] = 0u;
+            if (words && !((words[(size_t)by * C.wpr + (bx >> 5)] >> (bx & 31)) & 1u))
+                continue;
+            const WEntrySet S = wbvh_entry_block(nodes, nnodes, C, bx, by, K, fan, max_depth);
+            for (int i = 0; i < W_ENTRY_MAX; i++)
+                o[i] = S.link[i];
+        }
 }
 
 // A frame's two risk points (kernels.hip wide_risk_kernel): sel 0 the camera (rays start at it), sel
@@ -1286,6 +1442,9 @@ RT_HD T wg_read(T x, int i)
 // the final best: skipped soundly), so the group's lanes together test every triangle the G = 1 query
 // would need; the answer (minimum over the lanes' records, a tie when two lanes hold it or one lane saw
 // two) is the same on every lane of the group.
+// start (optional, one query per call): the nodes the walk starts at instead of the root: a
+// caller passes a set that every child the root query would enter for this ray lies below, with only inner
+// nodes above it; nullptr: the root.
 // No lane refill (the default): one query per call.
 struct WNoFeed {
     static constexpr bool on = false;
@@ -1300,7 +1459,7 @@ template <class Stack, int G = 1, class Feed = WNoFeed>
 RT_HD int wbvh_closest(const WNode* nodes, const GTri* tris, v3 o, v3 d, float m, Stack& stk, WHit& h,
                        uint32_t* work = nullptr, float hi = INFINITY, bool ties = true, float QS = 0x1p-8f,
                        const uint64_t* risk = nullptr, int rsel = 0, float rsub = 0.0f, uint32_t max_steps = 0,
-                       Feed* feed = nullptr, bool nob = false)
+                       Feed* feed = nullptr, bool nob = false, const uint32_t* start = nullptr)
 {
     static_assert(G == 1 || ((G & (G - 1)) == 0 && G <= 8 && (Stack::CAP & (Stack::CAP - 1)) == 0),
                   "a lane group: a power of two up to 8 lanes, a ring stack of 2^k entries");
@@ -1353,6 +1512,15 @@ RT_HD int wbvh_closest(const WNode* nodes, const GTri* tris, v3 o, v3 d, float m
     float dropped = INFINITY;   // the smallest key of the children a full stack could not take
     int sp = 0, bot = 0;        // the stack's entries [bot, sp) (bot > 0: entries taken by the group)
     uint32_t cur = FEED || (G > 1 && wg_lane<G>() != 0) ? W_EMPTY : 0u;   // root node (FEED: no query yet)
+    if (!FEED && start && cur != W_EMPTY) {
+        // the start set (wbvh_entry_block, W_ENTRY_MAX links, W_EMPTY in unused slots; G > 1: group lane 0
+        // holds it): the first link is visited now, the others wait on the stack with key 0 (never culled),
+        // the second on top
+        cur = start[0];
+        for (int i = W_ENTRY_MAX - 1; i >= 1; i--)
+            if (start[i] != W_EMPTY)
+                stk.put(slot(sp++), make_uint2(start[i], 0u));
+    }
     uint32_t nn = 0, nt = 0;
     uint32_t steps = 0;   // loop iterations (node or leaf visits)
     // the status of the lane's query once its loop is over (G = 1; the tail below for every G)

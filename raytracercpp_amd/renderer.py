@@ -483,6 +483,16 @@ class Renderer:
         bits = (words.reshape(bh, wpr)[:, :, None] >> np.arange(32, dtype=np.uint32)) & 1
         return bits.reshape(bh, wpr * 32)[:, :bw].astype(bool), {"on": bool(info[3]), "cut": int(info[4])}
 
+    def tile_starts(self, src=0):
+        """The last frame launch's entry sets (rt_tile_starts) -> (sets [block rows, blocks per row, 4] uint32,
+        on): the wide-BVH nodes each 8 x 8 block's camera rays start at (0xFFFFFFFF: unused slot; [0, ...]: the
+        root).  src 0: the device's, 1: the host's recomputation.  on False: the launch had no entry sets."""
+        info = np.zeros(3, np.int32)
+        self._call("rt_tile_starts", int(src), None, 0, ptr(info, _i32p))
+        sets = np.zeros((int(info[1]), int(info[0]), 4), np.uint32)
+        self._call("rt_tile_starts", int(src), ptr(sets, _u32p), sets.size, ptr(info, _i32p))
+        return sets, bool(info[2])
+
     # -- convenience ----------------------------------------------------------------
     def load_scene(self, sc: SceneData, st: RenderSettings):
         """Settings, camera, light, materials, geometry and textures of a SceneData."""

@@ -3,7 +3,10 @@ per primary ray (the camera's risk words) and per shadow ray (the light's), thei
 costliest 8x8 tiles' longest rays.  With RT_LIB_PATH pointing at a variant build (tools/variants.py
 build ...) the same rays price a variant of the child test.
     python tools/visit_probe.py [config] [tile_row_stride]
-Rays: every tile_row_stride-th row of 8x8 tiles (all 8 rows of each), so tile maxima are exact."""
+Rays: every tile_row_stride-th row of 8x8 tiles (all 8 rows of each), so tile maxima are exact.
+Then (RT_PROBE_ENTRY=0: not) the same primary rays started at their blocks' entry sets, per
+policy: visits per hit and per miss ray, the sets' sizes and depths, and the queries whose status differs from
+the root query's (profiles/entry_nodes/host_probe.log)."""
 import os
 import sys
 
@@ -55,6 +58,37 @@ def main():
           f" over 200: {int((tmax > 200).sum())}")
     print(f"  hit rays {nodes[hit].mean():.3f} visits/ray, misses {nodes[~hit].mean():.3f}; mean over tiles of the "
           f"longest ray {tmax.mean():.3f} (the waves' iterations: {tmax.mean() / max(nodes.mean(), 1e-9):.2f}x the mean ray)")
+    if os.environ.get("RT_PROBE_ENTRY", "1") != "0":
+        entry_table(name, sc, st, o, d, rows, rw, rh, st_, nodes)
+
+
+def entry_table(name, sc, st, o, d, rows, rw, rh, st_root, n_root):
+    """The same rays started at their blocks' entry sets, per policy (K nodes per block, a
+    frontier node expanded while at most 'fan' of its children cover the block)."""
+    pix = np.stack([np.tile(np.arange(rw), len(rows)), np.repeat(rows, rw)], 1).astype(np.int32)
+    hit = st_root == 1
+    blk = (pix[:, 1] >> 3) * ((rw + 7) // 8) + (pix[:, 0] >> 3)
+    print(f"  entry sets ({name}, {len(o)} rays; from the root: {n_root[hit].mean():.3f} visits per hit ray, "
+          f"{n_root[~hit].mean():.3f} per miss ray)")
+    print("  K fan | hit ray  miss ray  all rays | saved/hit | status differs | covered blocks: links 1/2/3/4, at the root | "
+          "link depth 1..12")
+    for k, fan in ((1, 1), (2, 2), (4, 1), (4, 2), (4, 3), (4, 4)):
+        nodes = np.zeros(len(o), np.int32)
+        e = dict(proj_inv=sc.proj_inv, cam_to_world=sc.cam_to_world, rw=rw, rh=rh, pixel=pix, k=k, fan=fan)
+        s2 = _lib.wbvh_query(sc.tri, o, d, st.bvh_max_depth, st.bvh_leaf_object_count, cam=sc.cam_pos, ray_nodes=nodes,
+                             entry=e)[0]
+        assert e["has_mask"], "the camera has no mask"
+        sets = e["sets"].reshape(-1, 4)
+        # the covered blocks among the probed rows: those whose set is not the bare root, or that hold a hit
+        probed = np.unique(blk)
+        ps = sets[probed]
+        nl = (ps != 0xFFFFFFFF).sum(1)
+        root = (ps[:, 0] == 0)
+        cov = ~root | np.isin(probed, np.unique(blk[hit]))
+        sizes = [int(((nl == i) & ~root & cov).sum()) for i in (1, 2, 3, 4)]
+        print(f"  {k} {fan}   | {nodes[hit].mean():7.3f}  {nodes[~hit].mean():7.3f}  {nodes.mean():7.3f}  | "
+              f"{n_root[hit].mean() - nodes[hit].mean():6.3f}    | {int((s2 != st_root).sum()):6d}         | "
+              f"{sizes[0]}/{sizes[1]}/{sizes[2]}/{sizes[3]}, {int((root & cov).sum())} | {e['depth_hist'][1:13]}")
 
 
 if __name__ == "__main__":
