@@ -139,16 +139,12 @@ int Renderer::mirror_from(Renderer& L)
     shape_ = L.shape_;
     shape_mat_ = L.shape_mat_;
     if (mir_geom_ != L.geom_ver_) {
-        // (the lead's positions may live on its device: object edits there leave its tri_ stale)
-        int rc = L.host_tris();
+        // (the lead's positions may live on its device: its host copy is brought up to date first)
+        const std::vector<float>* tri;
+        int rc = L.host_tris(tri);
         if (rc != RT_OK)
             return rc;
-        tri_ = L.tri_;
-        drop_device_positions();
-        tri_mat_ = L.tri_mat_;
-        tri_mat_lo_ = L.tri_mat_lo_;
-        tri_mat_hi_ = L.tri_mat_hi_;
-        tri_uv_ = L.tri_uv_;
+        geo_.copy_host_from(L.geo_);
         std::memcpy(prev_object_, L.prev_object_, sizeof(prev_object_));
         has_bvh_ = L.has_bvh_;
         geom_dirty_ = true;

@@ -170,6 +170,7 @@ int Renderer::init(std::string& err)
         e = hipDeviceGetAttribute(&num_cus_, hipDeviceAttributeMultiprocessorCount, device_);
     for (int i = 0; i < 4 && e == hipSuccess; i++)
         e = hipEventCreate(&ev_[i]);
+    geo_.init(device_, stream_);
     if (e == hipSuccess)
         e = risk_fence_.create();
     if (e == hipSuccess)
@@ -191,8 +192,6 @@ Renderer::~Renderer()
         if (e) hipEventDestroy(e);
     risk_fence_.destroy();
     cut_fence_.destroy();
-    for (auto& e : ingest_ev_)
-        if (e) hipEventDestroy(e);
     for (auto& e : ring_)
         if (e) hipEventDestroy(e);
     for (auto& b : band_slot_)
@@ -203,7 +202,6 @@ Renderer::~Renderer()
         if (ev) hipEventDestroy(ev);
     if (display_stream_) hipStreamDestroy(display_stream_);
     if (display_host_) hipHostFree(display_host_);
-    if (build_pin_) hipHostFree(build_pin_);
     for (void* q : display_old_)
         hipHostFree(q);
 }
@@ -246,7 +244,7 @@ int Renderer::set_settings(const rt_settings& s)
                        s.bvh_leaf_object_count != s_.bvh_leaf_object_count;
     s_ = s;
     if (bvh_changed)
-        geom_dirty_ = true, ++geom_ver_;
+        touch_geometry();
     return RT_OK;
 }
 
@@ -277,110 +275,31 @@ int Renderer::set_triangles(const float* tri9, const int32_t* mat, const float* 
         return fail(RT_EINVAL, "set_triangles: null arrays");
     if (n >= (int64_t)1 << 30)
         return fail(RT_EUNSUPPORTED, "set_triangles: more than 2^30 triangles");
-    tri_.assign(tri9, tri9 + 9 * n);
-    drop_device_positions();
-    set_attributes(mat, uv6, n);
-    return RT_OK;
-}
-
-// set_triangles' materials, texture coordinates and flags (the positions are the caller's business)
-void Renderer::set_attributes(const int32_t* mat, const float* uv6, int64_t n)
-{
-    tri_mat_.assign(mat, mat + n);
-    // the material range, checked by validate() before every launch without re-reading
-    // the per-triangle indices (a 1M-triangle scan per frame cost ~0.2 ms of host time)
-    tri_mat_lo_ = INT32_MAX;
-    tri_mat_hi_ = INT32_MIN;
-    for (int32_t m : tri_mat_) {
-        tri_mat_lo_ = std::min(tri_mat_lo_, m);
-        tri_mat_hi_ = std::max(tri_mat_hi_, m);
-    }
-    if (uv6)
-        tri_uv_.assign(uv6, uv6 + 6 * n);
-    else
-        tri_uv_.clear();
+    geo_.set_host(tri9, mat, uv6, n);
     has_bvh_ = s_.enable_bvh;
-    geom_dirty_ = true, ++geom_ver_;
-}
-
-// rt_set_triangles_device / rt_update_vertices_device: both arrays must be device memory of device_.
-// (A pointer the runtime does not know leaves a sticky error behind: cleared.)
-int Renderer::check_device_input(const void* d_verts, const void* d_idx)
-{
-    for (const void* p : {d_verts, d_idx}) {
-        if (!p)
-            continue;
-        hipPointerAttribute_t a{};
-        hipError_t e = hipPointerGetAttributes(&a, p);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(RT_EINVAL, "geometry input: not a device pointer");
-        }
-        if (a.type != hipMemoryTypeDevice)
-            return fail(RT_EINVAL, "geometry input: not device memory");
-        if (a.device != device_)
-            return fail(RT_EINVAL, "geometry input: memory of another device");
-    }
+    touch_geometry();
     return RT_OK;
 }
 
-// d_tri9_ [n][9] from the caller's device arrays, eagerly and in stream order: stream_ waits for the
-// caller's stream, the kernel runs on stream_, the caller's stream waits for the kernel.  The host waits
-// only for frames in flight on other streams that read d_tri9_ (the raster path).  On RT_OK the
-// positions' state is the device input's; the caller sets the rest of the geometry.
+// rt_set_triangles_device / rt_update_vertices_device: geo_'s positions from the caller's device arrays (both
+// must be memory of device_).  The host waits only for frames in flight on other streams that read the
+// resident positions (the raster path).  A failed input leaves no triangles.
 int Renderer::ingest_positions(const float* d_verts, int64_t nv, const int32_t* d_idx, int64_t n, hipStream_t stream)
 {
     hipError_t e = hipSetDevice(device_);
     if (e != hipSuccess)
         return hip_fail(e, "hipSetDevice");
-    int rc = check_device_input(d_verts, d_idx);
+    int rc = geo_.check_input(d_verts, d_idx, err_);
     if (rc != RT_OK)
         return rc;
     if (sync_slots() != RT_OK)
         return RT_EHIP;
-    for (hipEvent_t& ev : ingest_ev_)
-        if (!ev && (e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess)
-            return hip_fail(e, "hipEventCreate (geometry input)");
-    if ((e = d_ingest_flag_.reserve(4)) != hipSuccess)
-        return hip_fail(e, "hipMalloc (geometry input)");
-    // (from here the positions before are gone: growing d_tri9_ drops its contents)
-    pending_xf_.clear();
-    if ((e = d_tri9_.reserve((size_t)n * 36)) == hipSuccess && (e = hipEventRecord(ingest_ev_[0], stream)) == hipSuccess &&
-        (e = hipStreamWaitEvent(stream_, ingest_ev_[0], 0)) == hipSuccess &&
-        (e = hipMemsetAsync(d_ingest_flag_.p, 0, 4, stream_)) == hipSuccess &&
-        (e = rt_launch_gather_points(d_verts, nv, d_idx, d_tri9_.as<float>(), 3 * n, d_ingest_flag_.as<uint32_t>(),
-                                     stream_)) == hipSuccess &&
-        (e = hipEventRecord(ingest_ev_[1], stream_)) == hipSuccess)
-        e = hipStreamWaitEvent(stream, ingest_ev_[1], 0);
-    if (e != hipSuccess) {
-        // (neither the old positions nor the new ones are whole: no triangles)
-        tri_.clear();
-        drop_device_positions();
-        set_attributes(nullptr, nullptr, 0);
-        return hip_fail(e, "geometry input on the device");
+    // (a failure past the point where the old positions are gone left no triangles: a geometry change)
+    if ((rc = geo_.ingest(d_verts, nv, d_idx, n, stream, err_)) != RT_OK && geo_.count() == 0) {
+        has_bvh_ = s_.enable_bvh;
+        touch_geometry();
     }
-    ++device_ingests_;
-    tri9_current_ = tri_stale_ = true;
-    tri9_nonfinite_ = tri9_badidx_ = false;
-    ingest_flag_live_ = true;
-    return RT_OK;
-}
-
-// the ingest kernel's word, once per ingest, where the host waits for stream_ anyway
-int Renderer::read_ingest_flag()
-{
-    if (!ingest_flag_live_)
-        return RT_OK;
-    unsigned word = 0;
-    hipError_t e = hipSetDevice(device_);
-    if (e == hipSuccess)
-        e = read_u32(d_ingest_flag_.p, stream_, word);
-    if (e != hipSuccess)
-        return hip_fail(e, "geometry input on the device");
-    ingest_flag_live_ = false;
-    tri9_nonfinite_ = tri9_nonfinite_ || (word & 1u) != 0;
-    tri9_badidx_ = tri9_badidx_ || (word & 2u) != 0;
-    return RT_OK;
+    return rc;
 }
 
 int Renderer::set_triangles_device(const float* d_verts, int64_t nv, const int32_t* d_idx, const int32_t* mat,
@@ -397,14 +316,15 @@ int Renderer::set_triangles_device(const float* d_verts, int64_t nv, const int32
     int rc = ingest_positions(d_verts, nv, d_idx, n, stream);
     if (rc != RT_OK)
         return rc;
-    // (tri_ is stale and stays as it is: host_tris sizes and fills it when a host reader asks)
-    set_attributes(mat, uv6, n);
+    geo_.set_attributes(mat, uv6, n);
+    has_bvh_ = s_.enable_bvh;
+    touch_geometry();
     return RT_OK;
 }
 
 int Renderer::update_vertices_device(const float* d_verts, int64_t nv, const int32_t* d_idx, hipStream_t stream)
 {
-    const int64_t n = (int64_t)tri_mat_.size();
+    const int64_t n = geo_.count();
     if (nv < 0 || !d_verts)
         return fail(RT_EINVAL, "update_vertices_device: null array");
     if (n == 0)
@@ -414,7 +334,7 @@ int Renderer::update_vertices_device(const float* d_verts, int64_t nv, const int
     int rc = ingest_positions(d_verts, nv, d_idx, n, stream);
     if (rc != RT_OK)
         return rc;
-    geom_dirty_ = true, ++geom_ver_;
+    touch_geometry();
     return RT_OK;
 }
 
@@ -443,16 +363,11 @@ int Renderer::add_plane(float px, float py, float pz, float nx, float ny, float 
 // renderer.cpp:182-186
 int Renderer::clear_geometry()
 {
-    tri_.clear();
-    drop_device_positions();
-    tri_mat_.clear();
-    tri_mat_lo_ = INT32_MAX;
-    tri_mat_hi_ = INT32_MIN;
-    tri_uv_.clear();
+    geo_.clear();
     shape_kind_.clear();
     shape_.clear();
     shape_mat_.clear();
-    geom_dirty_ = true, ++geom_ver_;
+    touch_geometry();
     return RT_OK;
 }
 
@@ -494,7 +409,7 @@ int Renderer::set_exact(bool on)
 {
     poll_accel(true, true);   // (reads wb_)
     if (knobs_.exact && !on && knobs_.wbvh && wb_.nodes.empty() && !wb_on_device_ && s_.enable_bvh)
-        geom_dirty_ = true, ++geom_ver_;
+        touch_geometry();
     knobs_.exact = on;
     return RT_OK;
 }
@@ -554,13 +469,14 @@ void Renderer::get_camera_matrices(float pos[3], float proj_inv[16], float c2w[1
 
 // renderer.cpp:214-224: every triangle goes through object_transform * previous^-1,
 // then the BVH is rebuilt.
-// With the device build on and the positions resident (d_tri9_), the matrix is queued for the device
-// (apply_device_edits, before the next build or host reader) and tri_ is left stale.
+// With the device build on and the positions resident, the matrix is queued for the device copy (it runs
+// before the next build or host reader) and the host copy is left stale.
 int Renderer::set_object_transform(const float m[16])
 {
-    const bool on_device = knobs_.gpu_build && knobs_.gpu_xform && !lead_ && tri9_current_;
+    const bool on_device = knobs_.gpu_build && knobs_.gpu_xform && !lead_ && geo_.resident();
+    const std::vector<float>* tri;
     if (!on_device) {
-        int rc = host_tris();
+        int rc = host_tris(tri);
         if (rc != RT_OK)
             return rc;
     }
@@ -568,23 +484,12 @@ int Renderer::set_object_transform(const float m[16])
     mat::inverse(prev_object_, inv);
     std::memcpy(prev_object_, inv, sizeof(inv));
     mat::compose(m, prev_object_, t);
-    if (on_device) {
-        std::array<float, 16> q;
-        std::memcpy(q.data(), t, sizeof(t));
-        pending_xf_.push_back(q);
-        tri_stale_ = true;
-    } else {
-        size_t n = tri_.size() / 3;
-        std::vector<float> out(tri_.size());
-        mat::transform_points(t, tri_.data(), (int64_t)n, out.data());
-        tri_.swap(out);
-        // (a device input's bad index left zeros in tri_, which no host scan can tell from the caller's)
-        const bool badidx = tri9_badidx_;
-        drop_device_positions();
-        tri9_badidx_ = badidx;
-    }
+    if (on_device)
+        geo_.queue_transform(t);
+    else
+        geo_.transform_host(t);
     has_bvh_ = true;
-    geom_dirty_ = true, ++geom_ver_;
+    touch_geometry();
     std::memcpy(prev_object_, m, sizeof(prev_object_));
     return RT_OK;
 }
@@ -632,14 +537,14 @@ int Renderer::set_skybox(const int32_t w[6], const int32_t h[6], const float* co
 int Renderer::reconstruct_bvh_new()
 {
     has_bvh_ = true;
-    geom_dirty_ = true, ++geom_ver_;
+    touch_geometry();
     return RT_OK;
 }
 
 int Renderer::destroy_bvh()
 {
     has_bvh_ = false;
-    geom_dirty_ = true, ++geom_ver_;
+    touch_geometry();
     return RT_OK;
 }
 
@@ -992,8 +897,8 @@ int Renderer::adopt_from_lead()
         copy(d_nodes_, L.d_nodes_, (size_t)L.oct_nn_ * sizeof(GNode));
         copy(d_tris_, L.d_tris_, (size_t)L.oct_nt_ * sizeof(GTri));
         copy(d_tri_id_, L.d_tri_id_, (size_t)L.oct_nt_ * 4);
-        copy(d_tri_mat_, L.d_tri_mat_, tri_mat_.size() * 4);
-        copy(d_tri_uv_, L.d_tri_uv_, L.has_uv_dev_ ? tri_uv_.size() * 4 : 0);
+        copy(d_tri_mat_, L.d_tri_mat_, geo_.mat().size() * 4);
+        copy(d_tri_uv_, L.d_tri_uv_, L.has_uv_dev_ ? geo_.uv().size() * 4 : 0);
         if (e == hipSuccess)
             e = hipStreamSynchronize(stream_);
         if (e != hipSuccess)
@@ -1042,73 +947,28 @@ int Renderer::adopt_from_lead()
     return RT_OK;
 }
 
-// The octree by the device builder (octree_gpu.hpp): tri_ goes up through the pinned staging buffer,
-// the builder writes d_nodes_ / d_tris_ / d_tri_id_ in place, and the three arrays come back into oct_
-// (the quick wide BVH, the leaf cones and the background build read them on the host) in chunks, the
-// DMA of one chunk beside the host's copy of the one before.
+// The octree by the device builder (octree_gpu.hpp) from geo_'s device copy (staged on stream_ when it is not
+// resident already): the builder writes d_nodes_ / d_tris_ / d_tri_id_ in place, and the three arrays come
+// back into oct_ (the quick wide BVH, the leaf cones and the background build read them on the host) through
+// the pinned ring, the DMA of one chunk beside the host's copy of the one before.
 int Renderer::build_octree_device(int64_t n, bool& built)
 {
     built = false;
     if (!octree_device_supported(n, s_.bvh_max_depth))
         return RT_OK;
     hipError_t e = hipSuccess;
-    auto pin = [&](size_t bytes) {
-        if (bytes <= build_pin_bytes_)
-            return hipSuccess;
-        if (build_pin_)
-            (void)hipHostFree(build_pin_);
-        build_pin_ = nullptr;
-        build_pin_bytes_ = 0;
-        hipError_t pe = hipHostMalloc(&build_pin_, bytes, hipHostMallocDefault);
-        if (pe == hipSuccess)
-            build_pin_bytes_ = bytes;
-        else
-            build_pin_ = nullptr;
-        return pe;
-    };
-    constexpr size_t CHUNK = 4u << 20;
-    constexpr int RING = 4;
-    const size_t in_bytes = (size_t)n * 9 * 4;
     if (!oct_gpu_)
         oct_gpu_ = std::make_unique<OctreeGpuScratch>();
-    if ((e = pin(RING * CHUNK)) != hipSuccess || (e = d_tri9_.reserve(in_bytes)) != hipSuccess ||
-        (e = d_oct_info_.reserve(sizeof(OctreeDevInfo))) != hipSuccess)
+    const float* d_tri9 = nullptr;
+    int rc = geo_.device(stream_, true, "device octree build", d_tri9, err_);
+    if (rc != RT_OK)
+        return rc;
+    if ((e = geo_.ring().reserve()) != hipSuccess || (e = d_oct_info_.reserve(sizeof(OctreeDevInfo))) != hipSuccess)
         return hip_fail(e, "hipMalloc (device octree build)");
-    char* ring = static_cast<char*>(build_pin_);
-    hipEvent_t ev[RING] = {};
-    struct EvGuard {
-        hipEvent_t* ev;
-        ~EvGuard()
-        {
-            for (int i = 0; i < RING; i++)
-                if (ev[i]) (void)hipEventDestroy(ev[i]);
-        }
-    } guard{ev};
-    for (int i = 0; i < RING && e == hipSuccess; i++) e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
-    // staging: the host fills one chunk of the ring while the DMA takes the one before (not when the
-    // positions are resident already: a build before this one, or a device transform, left them there)
-    const bool staged = !tri9_current_;
-    const char* src = reinterpret_cast<const char*>(tri_.data());
-    for (size_t i = 0, off = 0; staged && e == hipSuccess && off < in_bytes; i++, off += CHUNK) {
-        const size_t len = std::min(CHUNK, in_bytes - off);
-        if (i >= RING)
-            e = hipEventSynchronize(ev[i % RING]);   // the slot's last upload has left it
-        if (e == hipSuccess) {
-            std::memcpy(ring + (i % RING) * CHUNK, src + off, len);
-            e = hipMemcpyAsync(d_tri9_.as<char>() + off, ring + (i % RING) * CHUNK, len, hipMemcpyHostToDevice, stream_);
-        }
-        if (e == hipSuccess)
-            e = hipEventRecord(ev[i % RING], stream_);
-    }
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(stream_);
-        return hip_fail(e, "upload (device octree build)");
-    }
-    tri9_current_ = true;   // (in stream order: every later reader of d_tri9_ follows stream_ or waits for it)
     if (!oct_dev_info_)
         oct_dev_info_ = std::make_unique<OctreeDevInfo>();
     OctreeDevInfo& info = *oct_dev_info_;
-    int rc = build_flat_octree_device(*oct_gpu_, d_tri9_.as<float>(), n, s_.bvh_max_depth, s_.bvh_leaf_object_count,
+    rc = build_flat_octree_device(*oct_gpu_, d_tri9, n, s_.bvh_max_depth, s_.bvh_leaf_object_count,
                                       d_nodes_, d_tris_, d_tri_id_, d_oct_info_.as<OctreeDevInfo>(), &info, stream_,
                                       &e);
     if (rc == OCT_GPU_UNSUPPORTED)
@@ -1127,40 +987,11 @@ int Renderer::build_octree_device(int64_t n, bool& built)
     oct_.stats.max_leaf = info.stats[3];
     oct_.stats.max_depth = info.stats[4];
     oct_.stats.nodes = info.stats[5];
-    // readback: a ring of pinned chunks, each copied out once its event has passed
-    struct Part {
-        char* dst;
-        const char* src;
-        size_t bytes;
-    } parts[3] = {{reinterpret_cast<char*>(oct_.nodes.data()), d_nodes_.as<char>(), oct_.nodes.size() * sizeof(GNode)},
-                  {reinterpret_cast<char*>(oct_.tris.data()), d_tris_.as<char>(), oct_.tris.size() * sizeof(GTri)},
-                  {reinterpret_cast<char*>(oct_.tri_id.data()), d_tri_id_.as<char>(), oct_.tri_id.size() * 4}};
-    struct Piece {
-        char* dst;
-        const char* src;
-        size_t bytes;
-    };
-    std::vector<Piece> pieces;
-    for (const Part& p : parts)
-        for (size_t off = 0; off < p.bytes; off += CHUNK)
-            pieces.push_back({p.dst + off, p.src + off, std::min(CHUNK, p.bytes - off)});
-    const size_t np = pieces.size();
-    for (size_t i = 0; e == hipSuccess && i < np + RING; i++) {
-        if (i >= RING) {   // piece i - RING has landed in the slot piece i takes next
-            const Piece& q = pieces[i - RING];
-            if ((e = hipEventSynchronize(ev[i % RING])) == hipSuccess)
-                std::memcpy(q.dst, ring + (i % RING) * CHUNK, q.bytes);
-        }
-        if (e == hipSuccess && i < np) {
-            e = hipMemcpyAsync(ring + (i % RING) * CHUNK, pieces[i].src, pieces[i].bytes, hipMemcpyDeviceToHost, stream_);
-            if (e == hipSuccess)
-                e = hipEventRecord(ev[i % RING], stream_);
-        }
-    }
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(stream_);
+    const PinnedRing::Part parts[3] = {{oct_.nodes.data(), d_nodes_.p, oct_.nodes.size() * sizeof(GNode)},
+                                       {oct_.tris.data(), d_tris_.p, oct_.tris.size() * sizeof(GTri)},
+                                       {oct_.tri_id.data(), d_tri_id_.p, oct_.tri_id.size() * 4}};
+    if ((e = geo_.ring().readback(parts, 3, stream_)) != hipSuccess)
         return hip_fail(e, "readback (device octree build)");
-    }
     built = true;
     return RT_OK;
 }
@@ -1172,7 +1003,7 @@ int Renderer::build_octree_device(int64_t n, bool& built)
 int Renderer::build_wide_device(bool& built)
 {
     built = false;
-    const int64_t n = (int64_t)tri_mat_.size();
+    const int64_t n = geo_.count();
     if (!oct_dev_info_ || !wbvh_quick_device_supported(n, s_.bvh_max_depth))
         return RT_OK;
     if (!wq_gpu_)
@@ -1238,76 +1069,29 @@ int Renderer::host_wide()
     return RT_OK;
 }
 
-// The queued object edits (set_object_transform with the device build on), applied to d_tri9_ where it
-// lies: one launch per matrix on stream_, in call order, then the kernel's word.
-int Renderer::apply_device_edits()
+// geo_'s host copy for a host reader (the host octree build, brute-force mode, a helper's mirror, the
+// host-path transform, rt_get_triangles)
+int Renderer::host_tris(const std::vector<float>*& tri)
 {
-    if (pending_xf_.empty())
-        return RT_OK;
-    hipError_t e = hipSetDevice(device_);
-    if (e != hipSuccess)
-        return hip_fail(e, "hipSetDevice");
-    // raster frames in flight on other streams read d_tri9_
-    if (sync_slots() != RT_OK)
+    // raster frames in flight on other streams read the positions the queued edits rewrite
+    if (geo_.edits_queued() && sync_slots() != RT_OK)
         return RT_EHIP;
-    if ((e = d_geom_flag_.reserve(4)) != hipSuccess)
-        return hip_fail(e, "hipMalloc (object transform)");
-    const int64_t npts = 3 * (int64_t)tri_mat_.size();   // (tri_ may be unsized: a device input)
-    e = hipMemsetAsync(d_geom_flag_.p, 0, 4, stream_);
-    size_t applied = 0;
-    while (e == hipSuccess && applied < pending_xf_.size()) {
-        e = rt_launch_xform_points(pending_xf_[applied].data(), d_tri9_.as<float>(), npts,
-                                   d_geom_flag_.as<uint32_t>(), stream_);
-        if (e == hipSuccess)
-            applied++;
-    }
-    // (a launch that failed leaves its matrix and the ones behind it queued)
-    pending_xf_.erase(pending_xf_.begin(), pending_xf_.begin() + applied);
-    device_xforms_ += (int64_t)applied;
-    unsigned word = 0;
-    if (e == hipSuccess)
-        e = read_u32(d_geom_flag_.p, stream_, word);
-    if (e != hipSuccess)
-        return hip_fail(e, "object transform on the device");
-    tri9_nonfinite_ = tri9_nonfinite_ || word != 0;
-    return RT_OK;
-}
-
-// tri_ brought up to date for a host reader (the host octree build, brute-force mode, a helper's mirror,
-// the host-path transform, rt_get_triangles): one download after the queued edits, when it is stale
-int Renderer::host_tris()
-{
-    if (!tri_stale_)
-        return RT_OK;
-    int rc = apply_device_edits();
-    if (rc != RT_OK)
-        return rc;
-    if ((rc = read_ingest_flag()) != RT_OK)
-        return rc;
-    tri_.resize(9 * tri_mat_.size());   // (a device input leaves tri_ as it was, of any size)
-    hipError_t e = hipSetDevice(device_);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(stream_);
-    if (e == hipSuccess && !tri_.empty())
-        e = hipMemcpy(tri_.data(), d_tri9_.p, tri_.size() * 4, hipMemcpyDeviceToHost);
-    if (e != hipSuccess)
-        return hip_fail(e, "download (device-transformed triangles)");
-    tri_stale_ = false;
-    return RT_OK;
+    return geo_.host(tri, err_);
 }
 
 int Renderer::get_triangles(float* tri9, int64_t* n)
 {
     if (!n)
         return fail(RT_EINVAL, "rt_get_triangles: null count");
-    *n = (int64_t)tri_mat_.size();
+    *n = geo_.count();
     if (!tri9)
         return RT_OK;
-    int rc = host_tris();
+    const std::vector<float>* tri;
+    int rc = host_tris(tri);
     if (rc != RT_OK)
         return rc;
-    if (!tri_.empty())
-        std::memcpy(tri9, tri_.data(), tri_.size() * 4);
+    if (!tri->empty())
+        std::memcpy(tri9, tri->data(), tri->size() * 4);
     return RT_OK;
 }
 
@@ -1348,22 +1132,12 @@ int Renderer::rebuild_geometry()
     poll_accel(true, true);
     drop_accel();
     auto t0 = std::chrono::steady_clock::now();
-    const int64_t n = (int64_t)tri_mat_.size();
-    // queued object edits first (frames in flight that read d_tri9_ have ended: ensure_device_scene's sync_slots)
-    int rc = apply_device_edits();
-    if (rc == RT_OK)
-        rc = read_ingest_flag();
+    const int64_t n = geo_.count();
+    // queued object edits and the refusals first (frames in flight that read the resident positions have
+    // ended: ensure_device_scene's sync_slots)
+    int rc = geo_.check(err_);
     if (rc != RT_OK)
         return rc;
-    // (while tri_ is stale the positions were written by a kernel, which kept the same test's word)
-    bool finite = !tri9_nonfinite_;
-    if (!tri_stale_)
-        for (float c : tri_)
-            finite = finite && std::isfinite(c);
-    if (!finite)
-        return fail(RT_EINVAL, "triangle with a non-finite vertex coordinate");
-    if (tri9_badidx_)
-        return fail(RT_EINVAL, "vertex index out of range");
     bool dev_built = false;
     if ((rc = build_octree(n, dev_built)) != RT_OK)
         return rc;
@@ -1374,7 +1148,7 @@ int Renderer::rebuild_geometry()
     oct_levels_ = oct_.levels;
     oct_root_ = oct_nn_ > 0 ? oct_.nodes[0] : GNode{};
     oct_stats_ = oct_.stats;
-    has_uv_dev_ = !tri_uv_.empty();
+    has_uv_dev_ = !geo_.uv().empty();
     // the uploads are enqueued (e: the first failure among them) and waited for once, below
     auto t1 = std::chrono::steady_clock::now();
     hipError_t e = hipSuccess;
@@ -1422,10 +1196,11 @@ int Renderer::build_octree(int64_t n, bool& dev_built)
                 return rc;
         }
         if (!dev_built) {
-            int rc = host_tris();
+            const std::vector<float>* tri;
+            int rc = host_tris(tri);
             if (rc != RT_OK)
                 return rc;
-            build_flat_octree(tri_.data(), n, s_.bvh_max_depth, s_.bvh_leaf_object_count, oct_);
+            build_flat_octree(tri->data(), n, s_.bvh_max_depth, s_.bvh_leaf_object_count, oct_);
         }
         if (oct_.levels > 31)
             return fail(RT_EUNSUPPORTED, "octree deeper than 31 levels");
@@ -1434,14 +1209,15 @@ int Renderer::build_octree(int64_t n, bool& dev_built)
         return RT_OK;
     }
     // brute-force mode (renderer.cpp:1021-1027): triangles in caller order, no nodes
-    int rc = host_tris();
+    const std::vector<float>* tri;
+    int rc = host_tris(tri);
     if (rc != RT_OK)
         return rc;
     oct_ = FlatOctree();
     oct_.tris.resize((size_t)n);
     oct_.tri_id.resize((size_t)n);
     for (int64_t i = 0; i < n; i++) {
-        const float* p = tri_.data() + 9 * i;
+        const float* p = tri->data() + 9 * i;
         v3 a = mk(p[0], p[1], p[2]), b = mk(p[3], p[4], p[5]), c = mk(p[6], p[7], p[8]);
         v3 ab = b - a, ac = c - a, nn = cross(b - a, c - a);
         GTri& g = oct_.tris[(size_t)i];
@@ -1461,8 +1237,8 @@ int Renderer::upload_octree_tables(bool dev_built, hipError_t& e)
     size_t nb = oct_.nodes.size() * sizeof(GNode), tb = oct_.tris.size() * sizeof(GTri);
     if ((e = d_nodes_.reserve(nb)) != hipSuccess || (e = d_tris_.reserve(tb)) != hipSuccess ||
         (e = d_tri_id_.reserve(oct_.tri_id.size() * 4)) != hipSuccess ||
-        (e = d_tri_mat_.reserve(tri_mat_.size() * 4)) != hipSuccess ||
-        (e = d_tri_uv_.reserve(tri_uv_.size() * 4)) != hipSuccess)
+        (e = d_tri_mat_.reserve(geo_.mat().size() * 4)) != hipSuccess ||
+        (e = d_tri_uv_.reserve(geo_.uv().size() * 4)) != hipSuccess)
         return hip_fail(e, "hipMalloc (scene)");
     hipSetDevice(device_);
     if (nb && !dev_built) e = hipMemcpyAsync(d_nodes_.p, oct_.nodes.data(), nb, hipMemcpyHostToDevice, stream_);
@@ -1470,10 +1246,10 @@ int Renderer::upload_octree_tables(bool dev_built, hipError_t& e)
         e = hipMemcpyAsync(d_tris_.p, oct_.tris.data(), tb, hipMemcpyHostToDevice, stream_);
     if (e == hipSuccess && !oct_.tri_id.empty() && !dev_built)
         e = hipMemcpyAsync(d_tri_id_.p, oct_.tri_id.data(), oct_.tri_id.size() * 4, hipMemcpyHostToDevice, stream_);
-    if (e == hipSuccess && !tri_mat_.empty())
-        e = hipMemcpyAsync(d_tri_mat_.p, tri_mat_.data(), tri_mat_.size() * 4, hipMemcpyHostToDevice, stream_);
-    if (e == hipSuccess && !tri_uv_.empty())
-        e = hipMemcpyAsync(d_tri_uv_.p, tri_uv_.data(), tri_uv_.size() * 4, hipMemcpyHostToDevice, stream_);
+    if (e == hipSuccess && !geo_.mat().empty())
+        e = hipMemcpyAsync(d_tri_mat_.p, geo_.mat().data(), geo_.mat().size() * 4, hipMemcpyHostToDevice, stream_);
+    if (e == hipSuccess && !geo_.uv().empty())
+        e = hipMemcpyAsync(d_tri_uv_.p, geo_.uv().data(), geo_.uv().size() * 4, hipMemcpyHostToDevice, stream_);
     return RT_OK;
 }
 
@@ -1537,7 +1313,7 @@ int Renderer::validate() const
             return RT_EUNSUPPORTED;
     int nmat = material_count();
     if (s_.shading_method == RT_SHADING) {
-        if (!tri_mat_.empty() && (tri_mat_lo_ < 0 || tri_mat_hi_ >= nmat))
+        if (geo_.mat_out_of_range(nmat))
             return RT_EINVAL;
         for (int32_t m : shape_mat_)
             if (m < 0 || m >= nmat)
@@ -1713,13 +1489,6 @@ int Renderer::launch_trace(const KParams& P, hipStream_t stream)
     if ((e = rt_launch_refl_level0(&P, L1.fr.as<FrameRec>(), L1.cnt.as<unsigned int>(), stream)) != hipSuccess)
         return hip_fail(e, "refl_level0_kernel launch");
     return refl_level1_finish(P, stream, "refl_level0_kernel", true);
-}
-
-// One 32-bit count of the stream's last kernels, on the host once they are done.
-hipError_t Renderer::read_u32(const void* dev, hipStream_t stream, unsigned& out)
-{
-    hipError_t e = hipMemcpyAsync(&out, dev, 4, hipMemcpyDeviceToHost, stream);
-    return e != hipSuccess ? e : hipStreamSynchronize(stream);
 }
 
 // Level 1's frames come from the launch's shading pass (refl_level0_kernel, raster_shade_kernel), at most
@@ -1910,20 +1679,14 @@ int Renderer::refl_level(const KParams& P, int level, int nframes, hipStream_t s
 int Renderer::launch_raster(const KParams& P, hipStream_t stream)
 {
     hipError_t e;
-    const int64_t n = (int64_t)tri_mat_.size();
-    if (!tri9_current_) {   // (else: resident from the device build's staging or a device transform)
-        int rc = host_tris();
-        if (rc != RT_OK)
-            return rc;
-        if ((e = d_tri9_.reserve(tri_.size() * 4)) != hipSuccess) return hip_fail(e, "hipMalloc (raster triangles)");
-        if (!tri_.empty() &&
-            (e = hipMemcpyAsync(d_tri9_.p, tri_.data(), tri_.size() * 4, hipMemcpyHostToDevice, stream)) != hipSuccess)
-            return hip_fail(e, "upload (raster triangles)");
-        tri9_current_ = true;
-    }
+    const int64_t n = geo_.count();
+    const float* d_tri9 = nullptr;
+    int rc = geo_.device(stream, false, "raster triangles", d_tri9, err_);   // (no edits queued: the scene is settled)
+    if (rc != RT_OK)
+        return rc;
     RasterArgs A;
     std::memset(&A, 0, sizeof(A));
-    A.tri9 = d_tri9_.as<float>();
+    A.tri9 = d_tri9;
     A.ntri = n;
     std::memcpy(A.proj, proj_, sizeof(A.proj));
     std::memcpy(A.w2c, w2c_, sizeof(A.w2c));
@@ -1981,7 +1744,7 @@ int Renderer::check_frame() const
     if (s_.shading_method == RT_SHADING && any_reflection(mats_) && s_.max_recursion_depth > 15)
         return RT_EUNSUPPORTED;
     if (s_.hybrid_rasterization_tracing) {
-        if (tri_mat_.size() >= ((size_t)1 << 27))
+        if (geo_.count() >= ((int64_t)1 << 27))
             return RT_EUNSUPPORTED;   // 12 pieces per triangle must index in 31 bits
         if (s_.shading_method == RT_SHADING && any_reflection(mats_) && !s_.enable_bvh)
             return RT_EUNSUPPORTED;   // the frame engine traces through the octree

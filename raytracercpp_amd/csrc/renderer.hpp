@@ -16,9 +16,11 @@
 #include <vector>
 
 #include "../../include/rt_mi355x.h"
+#include "devbuf.hpp"
 #include "kparams.hpp"
 #include "ocone.hpp"
 #include "octree.hpp"
+#include "tri_geometry.hpp"
 #include "wbvh.hpp"
 #include "wide_layout.hpp"
 
@@ -27,23 +29,6 @@ namespace rt {
 struct OctreeGpuScratch;   // octree_gpu.hpp
 struct OctreeDevInfo;
 struct WQuickGpuScratch;   // wbvh_quick_gpu.hpp
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    int device = 0;   // the device that holds p: the calling thread's when reserve allocated it
-    ~DevBuf();
-    hipError_t reserve(size_t n);   // grows (never shrinks); contents undefined after growth
-    void release();                 // frees under 'device' (the calling thread's current device afterwards)
-    template <class T> T* as() const { return static_cast<T*>(p); }
-    // exchanges the allocations (a copy would free one buffer twice)
-    void swap(DevBuf& o)
-    {
-        std::swap(p, o.p);
-        std::swap(bytes, o.bytes);
-        std::swap(device, o.device);
-    }
-};
 
 // The device-resident wide BVH (wbvh.hpp) as one value: the nodes, the triangle records in its leaf order and
 // their metadata (what frames read), the slot maps wide_gather_kernel reads (tmp) and the grazing-risk walk's
@@ -191,8 +176,8 @@ public:
     void set_device_build(bool on) { knobs_.gpu_build = on; }
     int64_t device_builds() const { return device_builds_; }
     int64_t device_wide_builds() const { return device_wide_builds_; }
-    int64_t device_transforms() const { return device_xforms_; }
-    int64_t device_ingests() const { return device_ingests_; }
+    int64_t device_transforms() const { return geo_.transforms(); }
+    int64_t device_ingests() const { return geo_.ingests(); }
     int64_t accel_builds() const { return accel_builds_; }
     // geometry changes build the octree and the quick wide BVH only (rt_set_accel_deferred)
     void set_accel_deferred(bool on) { knobs_.accel_defer = on; }
@@ -325,7 +310,6 @@ private:
     // level 1 around the launch's shading pass: its frame buffer and zeroed count, then the count and refl_level
     int refl_level1_begin(const KParams& P, hipStream_t stream);
     int refl_level1_finish(const KParams& P, hipStream_t stream, const char* what, bool run_empty);
-    static hipError_t read_u32(const void* dev, hipStream_t stream, unsigned& out);
     // frames in flight (render_bands_device): make 'stream' wait for every live slot's last
     // launch, or the host for all of them (before buffers that launches read are replaced)
     int wait_slots(hipStream_t stream);
@@ -369,13 +353,10 @@ private:
     uint64_t mir_accel_ = ~0ull;   // the lead's accel_ver_ copied
     int adopt_from_lead();
     int64_t host_builds_ = 0;      // host octree builds (rt_stats host_builds, helpers included)
-    // the device octree build (knobs_.gpu_build): its temporaries and totals, and the pinned buffer the
-    // triangles are staged through and the built arrays come back through
+    // the device octree build (knobs_.gpu_build): its temporaries and totals
     int64_t device_builds_ = 0;    // device octree builds (rt_get_device_builds)
     std::unique_ptr<OctreeGpuScratch> oct_gpu_;
     DevBuf d_oct_info_;
-    void* build_pin_ = nullptr;
-    size_t build_pin_bytes_ = 0;
     // builds oct_ and d_nodes_ / d_tris_ / d_tri_id_ on the device; built stays false when the
     // builder does not take the input (the caller builds on the host)
     int build_octree_device(int64_t n, bool& built);
@@ -389,45 +370,18 @@ private:
     WStats wb_dev_stats_;
     int build_wide_device(bool& built);
     int host_wide();
-    // Object edits on the device (geom_gpu.hip).  d_tri9_, the caller-order positions the
-    // device build and the raster path read, is their resident home: tri9_current_ while it holds the
-    // current geometry (after the device build's staging, the raster path's upload or a device
-    // transform; not after set_triangles / clear_geometry, a helper's mirror or a host-path transform).
-    // (A flag, not a geom_ver_: that version also moves with the BVH settings, which leave the
-    // positions alone.)  With the device build on, set_object_transform queues its matrix in
-    // pending_xf_ and leaves tri_ stale; apply_device_edits runs the queue, one launch per matrix in
-    // call order (composed matrices would round differently), and host_tris brings tri_ up to date for
-    // the host readers.  tri_stale_ implies tri9_current_.
-    std::vector<std::array<float, 16>> pending_xf_;
-    bool tri9_current_ = false, tri_stale_ = false;
-    bool tri9_nonfinite_ = false;   // a device transform wrote a non-finite coordinate (until the geometry is replaced)
-    DevBuf d_geom_flag_;            // the kernel's word
-    int64_t device_xforms_ = 0;     // matrices applied by the kernel (rt_get_device_transforms)
-    int apply_device_edits();
-    int host_tris();
-    // Geometry input on the device (gather_points_kernel): d_tri9_ written from the caller's
-    // device arrays in stream order, tri_ left stale and unsized (host_tris sizes it from tri_mat_).  The
-    // kernel's word (bit 0 a non-finite coordinate, bit 1 an index out of range) is read by the next
-    // build or host reader (read_ingest_flag) and is sticky until the geometry is replaced.
-    DevBuf d_ingest_flag_;
-    bool ingest_flag_live_ = false;   // the word has not been read since the last ingest
-    bool tri9_badidx_ = false;
-    int64_t device_ingests_ = 0;      // gather launches (rt_get_device_ingests)
-    hipEvent_t ingest_ev_[2] = {nullptr, nullptr};   // the caller's stream -> stream_, and back
-    void set_attributes(const int32_t* mat, const float* uv6, int64_t n);
-    int check_device_input(const void* d_verts, const void* d_idx);
+    // The triangles: count, positions (host and / or device, with the queued object edits) and attributes
+    // (tri_geometry.hpp; where the positions are: tri_state.hpp).  Its calls marked [slots]
+    // come after sync_slots().
+    TriGeometry geo_;
+    // the geometry changed: the next frame rebuilds (geom_ver_: what a helper has mirrored)
+    void touch_geometry() { geom_dirty_ = true, ++geom_ver_; }
+    // geo_'s host copy, brought up to date (object edits queued for the device run first)
+    int host_tris(const std::vector<float>*& tri);
     int ingest_positions(const float* d_verts, int64_t nv, const int32_t* d_idx, int64_t n, hipStream_t stream);
-    int read_ingest_flag();
     // Deferred refinement (rt_set_accel_deferred): the resident octree has had no background build started
     bool unrefined_ = false;
     int64_t accel_builds_ = 0;        // start_accel calls (rt_get_accel_builds)
-    // tri_ has just been given new contents: d_tri9_ and the queue belong to the geometry before
-    void drop_device_positions()
-    {
-        pending_xf_.clear();
-        tri9_current_ = tri_stale_ = tri9_nonfinite_ = false;
-        ingest_flag_live_ = tri9_badidx_ = false;
-    }
     struct MultiDev;
     std::unique_ptr<MultiDev> multi_;
     int num_cus_ = 256;
@@ -438,10 +392,6 @@ private:
     rt_settings s_;
 
     // scene (host copies; the reference Renderer copies its inputs too)
-    std::vector<float> tri_;
-    std::vector<int32_t> tri_mat_;
-    int32_t tri_mat_lo_ = INT32_MAX, tri_mat_hi_ = INT32_MIN;   // range of tri_mat_
-    std::vector<float> tri_uv_;
     std::vector<int32_t> shape_kind_;
     std::vector<float> shape_;
     std::vector<int32_t> shape_mat_;
@@ -532,9 +482,9 @@ private:
     int prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M);
     DevBuf d_dbg_;                          // diagnostic per-wave records (RT_DEBUG_WAVES)
     bool ssao_ready_ = false;   // the buffers hold the last frame's z / normals
-    // raster path: caller-order triangles, per-triangle piece counts / offsets, the piece
-    // table and its texcoords, the z-key buffer, the big-piece list, scan scratch
-    DevBuf d_tri9_, d_rcount_, d_roff_, d_pieces_, d_piece_uv_, d_zkey_, d_big_, d_scan_tmp_;
+    // raster path: per-triangle piece counts / offsets, the piece table and its texcoords, the z-key
+    // buffer, the big-piece list, scan scratch (the caller-order triangles: geo_)
+    DevBuf d_rcount_, d_roff_, d_pieces_, d_piece_uv_, d_zkey_, d_big_, d_scan_tmp_;
     bool want_rgba_ = false, want_hit_ = false, want_shadow_ = false;
     bool aux_valid_ = false;
     // current image (Renderer::_image): internal from the start of ray_trace, downscaled after
