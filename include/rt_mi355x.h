@@ -432,6 +432,41 @@ int rt_band_costs(rt_renderer *r, void *hip_stream, double *costs, int32_t nband
 int rt_trace_rays(rt_renderer *r, const float *orig, const float *dir, int64_t n, int32_t *tri_id, float *t,
                   float *u, float *v, uint8_t *ret);
 
+/* Ray queries on device memory (no reference counterpart).
+ * rt_trace_rays_device is rt_trace_rays with every array in memory of the handle's device: d_orig / d_dir
+ * [n][3] floats in, d_tri_id / d_t / d_u / d_v / d_ret [n] out.  Per ray it writes exactly what rt_trace_rays
+ * writes for that ray in the same renderer state (the caller's triangle index or -1, the record's t / u / v --
+ * -1, 1, 0 for a miss the wide BVH certifies -- and the boolean BVH::intersect returned), in every mode: the
+ * resident wide BVH (quick or SAH tree), before one is resident, exact mode, RT_WBVH=0, enable_bvh 0.  It
+ * takes the frames' query (the certified wide-BVH query, the exact octree walk for what that cannot certify;
+ * DESIGN.md 5.6), where rt_trace_rays walks the octree for every ray.
+ * d_counts (int64 [2] in device memory, or NULL; the caller zeroes it): the kernel adds to [0] the rays the
+ * certified wide query answered and to [1] the rays traced through the octree walk or the brute-force loop;
+ * one call's two increments sum to n.
+ * rt_is_shadowed_device is Renderer::is_shadowed(inter_point, normal, light_position) (renderer.cpp:340-402)
+ * for n (d_point, d_normal) pairs ([n][3] floats): d_shadowed[i] = 1 where it returns true, analytic shapes
+ * included, else 0; all 0 with compute_shadows off, as the reference's function returns.  light: 3 host floats
+ * read during the call, NULL = the scene's light (rt_set_light_position).  The scene is checked only as far
+ * as is_shadowed reads it: no material or texture is needed.
+ * hip_stream is the caller's hipStream_t (NULL: the null stream).  The kernel is launched on it, after the
+ * work queued there before the call and before the work queued after it; only the caller's memory is
+ * written, and the host does not wait for the kernel.  The call may block the host for what a frame would
+ * block on (a pending geometry rebuild, a material upload) and allocates no device memory.  Whatever later
+ * replaces what the kernel reads (geometry, materials, the wide BVH, the risk words) and rt_destroy first
+ * wait for it, as for band launches, so the stream may be destroyed right after the call.
+ * Every pointer must be device memory of the handle's device (hipPointerGetAttributes on the pointer itself:
+ * that [n] elements lie behind it is the caller's word): else RT_EINVAL and no launch.  Outputs must not overlap the inputs or each other (not checked).  RT_EINVAL for a null pointer
+ * with n > 0, n < 0 or n > 2^30; n == 0: RT_OK, no launch, pointers unread, counters unchanged.  Errors a
+ * frame reports come back with the same codes (a non-finite ingested vertex, no usable device).  With
+ * rt_set_devices the queries run on the handle's own device only, as rt_trace_rays.
+ * rt_get_device_ray_queries: calls[0..1] = launches of the two kernels (closest hit, shadow) since
+ * rt_create, rays[0..1] = the rays given to them. */
+int rt_trace_rays_device(rt_renderer *r, const float *d_orig, const float *d_dir, int64_t n, int32_t *d_tri_id,
+                         float *d_t, float *d_u, float *d_v, uint8_t *d_ret, int64_t *d_counts, void *hip_stream);
+int rt_is_shadowed_device(rt_renderer *r, const float *d_point, const float *d_normal, int64_t n, const float *light,
+                          uint8_t *d_shadowed, void *hip_stream);
+int rt_get_device_ray_queries(rt_renderer *r, int64_t calls[2], int64_t rays[2]);
+
 /* Renderer::trace_ray(ray, hit_info, current_recursion_depth, intersection_found)
  * (renderer.h:144, renderer.cpp:1008-1066) for n arbitrary rays (origins / directions [n][3]),
  * each with a fresh HitInfo: rgba [n][4] = the Color trace_ray returns (shading, shadow ray,

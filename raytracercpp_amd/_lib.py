@@ -139,6 +139,10 @@ SIGNATURES = {
     "rt_render_band_list_device": (C.c_int, [_H, C.c_int32, _i32p, C.c_int32, C.c_void_p, C.c_void_p]),
     "rt_band_costs": (C.c_int, [_H, C.c_void_p, C.POINTER(C.c_double), C.c_int32]),
     "rt_trace_rays": (C.c_int, [_H, _f32p, _f32p, C.c_int64, _i32p, _f32p, _f32p, _f32p, _u8p]),
+    "rt_trace_rays_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_is_shadowed_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, _f32p, C.c_void_p, C.c_void_p]),
+    "rt_get_device_ray_queries": (C.c_int, [_H, _i64p, _i64p]),
     "rt_trace_ray": (C.c_int, [_H, _f32p, _f32p, C.c_int64, C.c_int32, _f32p, _i32p, _f32p, _u8p, _u8p]),
     "rt_wide_query": (C.c_int, [_H, _f32p, _f32p, C.c_int64, C.c_int32, _f32p, _f32p, _i32p, _i32p, _f32p, _f32p, _f32p,
                                 _u8p]),
@@ -184,6 +188,8 @@ SIGNATURES = {
 # row against another commit's library) may lack them; the in-tree library must have every symbol
 GEOMETRY_INPUT = ("rt_set_triangles_device", "rt_update_vertices_device", "rt_get_device_ingests",
                   "rt_gather_triangles_device", "rt_set_accel_deferred", "rt_get_accel_builds")
+# the device ray queries, likewise (tools/ray_query_time.py skips their rows for such a library)
+RAY_QUERIES = ("rt_trace_rays_device", "rt_is_shadowed_device", "rt_get_device_ray_queries")
 
 _lib = None
 
@@ -208,7 +214,7 @@ def lib():
             pass
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            if name in GEOMETRY_INPUT and os.environ.get("RT_LIB_PATH") and not hasattr(L, name):
+            if name in GEOMETRY_INPUT + RAY_QUERIES and os.environ.get("RT_LIB_PATH") and not hasattr(L, name):
                 continue
             fn = getattr(L, name)
             fn.restype = res
@@ -351,6 +357,59 @@ def device_geometry_args(verts, indices, device):
         return verts.data_ptr(), 3 * verts.shape[0], None, verts.shape[0]
     place(indices, "indices")
     return verts.data_ptr(), verts.shape[0], indices.data_ptr(), indices.shape[0]
+
+
+def device_ray_args(a, b, device, names=("orig", "dirs")):
+    """The checks of Renderer.trace_rays_device / is_shadowed_device on their two torch tensors (origins and
+    directions, or points and normals): (a pointer, b pointer, n).  Both float32 [n, 3] with the same n,
+    contiguous, on the GPU with index ``device``.  TypeError for a non-tensor or a wrong dtype, ValueError for
+    the wrong place, layout, shape or count."""
+    import torch
+
+    for t, name in zip((a, b), names):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: a torch tensor on the GPU is needed, not {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name}: dtype {t.dtype}, torch.float32 is needed")
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError(f"{name}: shape {tuple(t.shape)}, [n, 3] is needed")
+    if a.shape[0] != b.shape[0]:
+        raise ValueError(f"{names[0]} has {a.shape[0]} rows, {names[1]} {b.shape[0]}")
+    # (what each tensor is, its layout included, before where it lies: a [3, n] tensor transposed has the right
+    # shape and would be read as other rays, and the mistake shows without a GPU)
+    for t, name in zip((a, b), names):
+        _contiguous(t, name)
+    for t, name in zip((a, b), names):
+        _device_place(t, name, device)
+    return a.data_ptr(), b.data_ptr(), a.shape[0]
+
+
+def _contiguous(t, name):
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: the tensor is not contiguous")
+
+
+def _device_place(t, name, device):
+    if not t.is_cuda:
+        raise ValueError(f"{name}: the tensor is on {t.device}, not on a GPU")
+    if t.device.index != int(device):
+        raise ValueError(f"{name}: the tensor is on GPU {t.device.index}, the renderer on GPU {int(device)}")
+
+
+def device_ray_out(t, name, dtype, n, device):
+    """An output tensor of a device ray query: ``dtype``, one dimension, at least n elements, placed as the
+    inputs; its pointer."""
+    import torch
+
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: a torch tensor on the GPU is needed, not {type(t).__name__}")
+    if t.dtype != dtype:
+        raise TypeError(f"{name}: dtype {t.dtype}, {dtype} is needed")
+    if t.dim() != 1 or t.shape[0] < n:
+        raise ValueError(f"{name}: shape {tuple(t.shape)}, [>= {n}] is needed")
+    _contiguous(t, name)
+    _device_place(t, name, device)
+    return t.data_ptr()
 
 
 def load_obj(path, xform, mat_offset=0):

@@ -457,6 +457,30 @@ int rt_trace_rays(rt_renderer* r, const float* orig, const float* dir, int64_t n
 {
     return guarded(R(r), [&] { return R(r)->trace_rays(orig, dir, n, tri_id, t, u, v, ret); });
 }
+int rt_trace_rays_device(rt_renderer* r, const float* d_orig, const float* d_dir, int64_t n, int32_t* d_tri_id,
+                         float* d_t, float* d_u, float* d_v, uint8_t* d_ret, int64_t* d_counts, void* hip_stream)
+{
+    return guarded(R(r), [&] {
+        return R(r)->trace_rays_device(d_orig, d_dir, n, d_tri_id, d_t, d_u, d_v, d_ret, d_counts,
+                                       reinterpret_cast<hipStream_t>(hip_stream));
+    });
+}
+int rt_is_shadowed_device(rt_renderer* r, const float* d_point, const float* d_normal, int64_t n, const float* light,
+                          uint8_t* d_shadowed, void* hip_stream)
+{
+    return guarded(R(r), [&] {
+        return R(r)->is_shadowed_device(d_point, d_normal, n, light, d_shadowed, reinterpret_cast<hipStream_t>(hip_stream));
+    });
+}
+int rt_get_device_ray_queries(rt_renderer* r, int64_t calls[2], int64_t rays[2])
+{
+    return guarded(R(r), [&] {
+        if (!calls || !rays)
+            return RT_EINVAL;
+        R(r)->device_ray_queries(calls, rays);
+        return RT_OK;
+    });
+}
 int rt_wide_query(rt_renderer* r, const float* orig, const float* dir, int64_t n, int32_t kind, float* o_out,
                   float* d_out, int32_t* status, int32_t* tri_id, float* t, float* u, float* v, uint8_t* shadowed)
 {

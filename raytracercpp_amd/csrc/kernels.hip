@@ -1198,7 +1198,10 @@ __device__ __forceinline__ OctQ octree_query(const KParams& P, v3 o, v3 d, float
 
 // renderer.cpp:340-402
 // OCT: the octree walk only (ray_trace_kernel's octree specialisation: no wide-BVH code)
-template <bool PLAIN = false, int G = 1, bool CALL = PLAIN, bool OCT = false>
+// COPY: a caller's own instance of the same code (shadow_points_kernel).  Another call of an instance the
+// shaded kernels share changes which of them the compiler inlines into whom, and with that the code and the
+// spills of kernels that did not change (tools/device_code_diff.py).
+template <bool PLAIN = false, int G = 1, bool CALL = PLAIN, bool OCT = false, int COPY = 0>
 __device__ bool is_shadowed(const KParams& P, v3 p, v3 n, v3 lp, uint2* lv)
 {
     if (!P.compute_shadows)
@@ -3605,6 +3608,93 @@ __global__ __launch_bounds__(BLOCK, RT_OCC_PLAIN) void wide_query_kernel(KParams
     out_sh[i] = sh;
 }
 
+// BVH::intersect for a batch of rays that lie in the caller's device memory (rt_trace_rays_device): per
+// ray what trace_rays_kernel writes, answered the way the frames answer it -- the certified wide query
+// (wide_closest, which applies everything keyed on the origin being P.cam_pos), the exact octree walk for
+// what that cannot certify, for a NaN ray and when no wide BVH is resident; the brute-force loop when
+// enable_bvh is off.  counts (optional): [0] += rays the wide query answered, [1] += the others, one
+// atomic per wave and word, so no lane leaves before the wave's ballots.
+// (The occupancy bound is the plain kernel's, which wide_closest_deep's callers already have; see
+// wide_query_kernel.  With both walks inlined the kernel takes 132 VGPRs and spills none; at RT_OCC's 96
+// it spilled 57 of them.)
+__global__ __launch_bounds__(BLOCK, RT_OCC_PLAIN) void closest_rays_kernel(KParams P_arg, const float* __restrict__ orig,
+                                                                           const float* __restrict__ dir, int n,
+                                                                           int32_t* __restrict__ out_id,
+                                                                           float* __restrict__ out_t, float* __restrict__ out_u,
+                                                                           float* __restrict__ out_v,
+                                                                           uint8_t* __restrict__ out_ret,
+                                                                           unsigned long long* __restrict__ counts)
+{
+    const KParams& P = kernel_params();
+    (void)P_arg;
+    uint2* lv = lane_stack();
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    bool wide = false;
+    if (i < n) {
+        // (n goes up to 2^30: 3 * i does not fit 32 bits past i = 715,827,882)
+        const size_t j = 3 * (size_t)i;
+        const v3 o = mk(orig[j], orig[j + 1], orig[j + 2]);
+        const v3 d = mk(dir[j], dir[j + 1], dir[j + 2]);
+        THit h;
+        bool r = false;
+        if (P.enable_bvh) {
+            if (P.wnodes && P.nnodes > 0 && !ray_is_nan(o, d))
+                wide = wide_closest<1, W_STACK, false>(P, o, d, h, r, lv);
+            if (!wide) {
+                const OctQ q = octree_query<false>(P, o, d, 0.0f, 0.0f, false, lv);
+                h = q.h;
+                r = q.r;
+            }
+        } else {
+            const TRay R = make_ray(P, o, d);
+            h.t = -1.0f; h.u = 1.0f; h.v = 0.0f; h.k = -1;
+            for (int k = 0; k < P.ntri_slots; k++) {
+                float t, u, v;
+                if (tri_test(P.tris, (uint32_t)k, R, t, u, v))
+                    if (t < h.t || h.t == -1) {
+                        h.t = t; h.u = u; h.v = v; h.k = k;
+                    }
+            }
+            r = h.k >= 0;
+        }
+        out_id[i] = h.k >= 0 ? P.tri_id[h.k] : -1;
+        out_t[i] = h.t;
+        out_u[i] = h.u;
+        out_v[i] = h.v;
+        out_ret[i] = r ? 1 : 0;
+    }
+    if (counts) {
+        const unsigned long long nw = (unsigned long long)__popcll(__ballot(wide));
+        const unsigned long long no = (unsigned long long)__popcll(__ballot(i < n && !wide));
+        if (__lane_id() == 0) {
+            if (nw) atomicAdd(&counts[0], nw);
+            if (no) atomicAdd(&counts[1], no);
+        }
+    }
+}
+
+// Renderer::is_shadowed(inter_point, normal, light_position) (renderer.cpp:340-402) for a batch of
+// (point, normal) pairs in the caller's device memory (rt_is_shadowed_device): the generic query of the
+// shaded kernels with the call's light, which reads the frame's light risk words only when that light
+// is P.light.  It takes an instance of its own (is_shadowed's COPY), which leaves the shaded kernels'
+// code as it was.  (The same bound as closest_rays_kernel: 145 VGPRs, none spilled.)
+__global__ __launch_bounds__(BLOCK, RT_OCC_PLAIN) void shadow_points_kernel(KParams P_arg, const float* __restrict__ point,
+                                                                            const float* __restrict__ normal, int n,
+                                                                            float lx, float ly, float lz,
+                                                                            uint8_t* __restrict__ out_sh)
+{
+    const KParams& P = kernel_params();
+    (void)P_arg;
+    uint2* lv = lane_stack();
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n)
+        return;
+    const size_t j = 3 * (size_t)i;   // (in 64 bits, as closest_rays_kernel)
+    const v3 p = mk(point[j], point[j + 1], point[j + 2]);
+    const v3 nrm = mk(normal[j], normal[j + 1], normal[j + 2]);
+    out_sh[i] = is_shadowed<false, 1, false, false, 1>(P, p, nrm, mk(lx, ly, lz), lv) ? 1 : 0;
+}
+
 // Renderer::trace_ray (renderer.cpp:1008-1066) for a batch of arbitrary rays, one lane per
 // ray, each with a fresh HitInfo: the colour trace_ray returns (shading, shadow ray, the
 // compute_reflection recursion when REFL), and the record it leaves.  The host folds
@@ -3785,6 +3875,28 @@ hipError_t rt_launch_wide_query(const rt::KParams* P, const float* o, const floa
     else if (G == 4) RT_WQ(4);
     else RT_WQ(8);
 #undef RT_WQ
+    return hipGetLastError();
+}
+
+hipError_t rt_launch_closest_rays(const rt::KParams* P, const float* o, const float* d, int n, int32_t* id, float* t,
+                                  float* u, float* v, uint8_t* ret, int64_t* counts, hipStream_t stream)
+{
+    if (n <= 0)
+        return hipSuccess;
+    size_t lds = rt::lds_bytes(*P);
+    hipLaunchKernelGGL(rt::closest_rays_kernel, dim3((n + rt::BLOCK - 1) / rt::BLOCK), dim3(rt::BLOCK), lds, stream, *P,
+                       o, d, n, id, t, u, v, ret, reinterpret_cast<unsigned long long*>(counts));
+    return hipGetLastError();
+}
+
+hipError_t rt_launch_shadow_points(const rt::KParams* P, const float* point, const float* normal, int n,
+                                   const float light[3], uint8_t* shadowed, hipStream_t stream)
+{
+    if (n <= 0)
+        return hipSuccess;
+    size_t lds = rt::lds_bytes(*P);
+    hipLaunchKernelGGL(rt::shadow_points_kernel, dim3((n + rt::BLOCK - 1) / rt::BLOCK), dim3(rt::BLOCK), lds, stream, *P,
+                       point, normal, n, light[0], light[1], light[2], shadowed);
     return hipGetLastError();
 }
 

@@ -42,6 +42,11 @@ RT_LAUNCH rt_launch_trace_rays(const rt::KParams* P, const float* o, const float
 RT_LAUNCH rt_launch_wide_query(const rt::KParams* P, const float* o, const float* d, int n, int kind, float* o_out,
                                float* d_out, int32_t* status, int32_t* id, float* t, float* u, float* v, uint8_t* sh,
                                hipStream_t stream);
+// the ray queries over the caller's device memory (rt_trace_rays_device, rt_is_shadowed_device)
+RT_LAUNCH rt_launch_closest_rays(const rt::KParams* P, const float* o, const float* d, int n, int32_t* id, float* t,
+                                 float* u, float* v, uint8_t* ret, int64_t* counts, hipStream_t stream);
+RT_LAUNCH rt_launch_shadow_points(const rt::KParams* P, const float* point, const float* normal, int n,
+                                  const float light[3], uint8_t* shadowed, hipStream_t stream);
 RT_LAUNCH rt_launch_trace_colors(const rt::KParams* P, bool refl, const float* o, const float* d, int n, float4* rgba,
                                  int32_t* src, float* t, uint8_t* found, uint8_t* shadow, hipStream_t stream);
 RT_LAUNCH rt_launch_downscale(const uint32_t* in, int w, int h_rows, int f, uint32_t* out, hipStream_t stream);

@@ -175,6 +175,8 @@ int Renderer::init(std::string& err)
         e = risk_fence_.create();
     if (e == hipSuccess)
         e = cut_fence_.create();
+    if (e == hipSuccess)
+        e = query_fence_.create();
     if (e != hipSuccess) {
         err = std::string("HIP init failed: ") + hipGetErrorString(e);
         return RT_EHIP;
@@ -187,11 +189,13 @@ Renderer::~Renderer()
     if (accel_thread_.joinable())
         accel_thread_.join();
     hipSetDevice(device_);
+    sync_slots();   // launches in flight on the callers' streams read the buffers freed below
     if (accel_stream_) hipStreamDestroy(accel_stream_);
     for (auto& e : ev_)
         if (e) hipEventDestroy(e);
     risk_fence_.destroy();
     cut_fence_.destroy();
+    query_fence_.destroy();
     for (auto& e : ring_)
         if (e) hipEventDestroy(e);
     for (auto& b : band_slot_)
@@ -2620,6 +2624,9 @@ int Renderer::wait_slots(hipStream_t stream)
         if (e != hipSuccess)
             return hip_fail(e, "hipStreamWaitEvent (frames in flight)");
     }
+    hipError_t e = query_fence_.wait_on(stream);
+    if (e != hipSuccess)
+        return hip_fail(e, "hipStreamWaitEvent (ray queries in flight)");
     return RT_OK;
 }
 
@@ -2630,6 +2637,9 @@ int Renderer::sync_slots()
         if (e != hipSuccess)
             return hip_fail(e, "hipEventSynchronize (frames in flight)");
     }
+    hipError_t e = query_fence_.sync();
+    if (e != hipSuccess)
+        return hip_fail(e, "hipEventSynchronize (ray queries in flight)");
     return RT_OK;
 }
 
@@ -2671,6 +2681,78 @@ int Renderer::trace_rays(const float* orig, const float* dir, int64_t n, int32_t
     if ((e = hipStreamSynchronize(stream_)) != hipSuccess)
         return hip_fail(e, "trace_rays_kernel");
     return RT_OK;
+}
+
+// Before a device ray query's launch (rt_trace_rays_device, rt_is_shadowed_device).  Nothing
+// of the scene is validated beyond what a frame's ensure_device_scene refuses: like trace_rays, the queries
+// read the triangles and the analytic shapes only, no material and no texture.
+int Renderer::begin_ray_query(const char* what, const void* const* ptrs, int nptrs, int n_required, int64_t n,
+                              hipStream_t stream, KParams& P)
+{
+    bool null_arg = false;
+    for (int i = 0; i < n_required; i++)
+        null_arg = null_arg || !ptrs[i];
+    // (n up to 2^30 fits the kernels' int lane index; they index the [n][3] arrays in 64 bits, 3 n being past
+    // 2^31 from n = 715,827,883)
+    if (n < 0 || n > (1 << 30) || (n > 0 && null_arg))
+        return fail(RT_EINVAL, std::string(what) + ": bad arguments");
+    // every pointer is memory of device_ (the check of the geometry input)
+    int rc = n > 0 ? check_device_pointers(ptrs, nptrs, device_, what, err_) : RT_OK;
+    if (rc != RT_OK)
+        return rc;
+    rc = ensure_device_scene();
+    if (rc != RT_OK || n == 0)
+        return rc;
+    fill_params(P);
+    // (the stream waits for the risk words' computation, or computes them after the launches that read the
+    // old ones: rays from the camera position and shadow rays to the scene's light read them)
+    return prepare_risk(P, stream);
+}
+
+int Renderer::end_ray_query(int kind, int64_t n, hipStream_t stream)
+{
+    hipError_t e = query_fence_.record(stream, fence_stream_);
+    if (e != hipSuccess)
+        return hip_fail(e, "hipEventRecord (ray query)");
+    query_calls_[kind]++;
+    query_rays_[kind] += n;
+    return RT_OK;
+}
+
+int Renderer::trace_rays_device(const float* d_orig, const float* d_dir, int64_t n, int32_t* d_id, float* d_t,
+                                float* d_u, float* d_v, uint8_t* d_ret, int64_t* d_counts, hipStream_t stream)
+{
+    const void* const ptrs[] = {d_orig, d_dir, d_id, d_t, d_u, d_v, d_ret, d_counts};
+    KParams P;
+    int rc = begin_ray_query("trace_rays_device", ptrs, 8, 7, n, stream, P);
+    if (rc != RT_OK || n == 0)
+        return rc;
+    hipError_t e = rt_launch_closest_rays(&P, d_orig, d_dir, (int)n, d_id, d_t, d_u, d_v, d_ret, d_counts, stream);
+    if (e != hipSuccess)
+        return hip_fail(e, "closest_rays_kernel launch");
+    return end_ray_query(0, n, stream);
+}
+
+int Renderer::is_shadowed_device(const float* d_point, const float* d_normal, int64_t n, const float* light,
+                                 uint8_t* d_shadowed, hipStream_t stream)
+{
+    const void* const ptrs[] = {d_point, d_normal, d_shadowed};
+    KParams P;
+    int rc = begin_ray_query("is_shadowed_device", ptrs, 3, 3, n, stream, P);
+    if (rc != RT_OK || n == 0)
+        return rc;
+    hipError_t e = rt_launch_shadow_points(&P, d_point, d_normal, (int)n, light ? light : P.light, d_shadowed, stream);
+    if (e != hipSuccess)
+        return hip_fail(e, "shadow_points_kernel launch");
+    return end_ray_query(1, n, stream);
+}
+
+void Renderer::device_ray_queries(int64_t calls[2], int64_t rays[2]) const
+{
+    for (int k = 0; k < 2; k++) {
+        calls[k] = query_calls_[k];
+        rays[k] = query_rays_[k];
+    }
 }
 
 // The frames' wide-BVH query with its status over n host rays (kernels.hip wide_query_kernel): the

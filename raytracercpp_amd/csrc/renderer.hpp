@@ -268,6 +268,16 @@ public:
     // BVH::intersect over n host rays (closest hit, reference semantics)
     int trace_rays(const float* orig, const float* dir, int64_t n, int32_t* id, float* t, float* u, float* v,
                    uint8_t* ret);
+    // The ray queries over memory of device_, launched on the caller's stream (rt_trace_rays_device,
+    // rt_is_shadowed_device): trace_rays' outputs through the frames' query, and
+    // Renderer::is_shadowed (renderer.cpp:340-402) per (point, normal) pair towards 'light' (3 host floats,
+    // null: the scene's).  The host does not wait for the kernel; query_fence_ follows it.
+    int trace_rays_device(const float* d_orig, const float* d_dir, int64_t n, int32_t* d_id, float* d_t, float* d_u,
+                          float* d_v, uint8_t* d_ret, int64_t* d_counts, hipStream_t stream);
+    int is_shadowed_device(const float* d_point, const float* d_normal, int64_t n, const float* light,
+                           uint8_t* d_shadowed, hipStream_t stream);
+    // launches of the two kernels since rt_create and the rays given to them (rt_get_device_ray_queries)
+    void device_ray_queries(int64_t calls[2], int64_t rays[2]) const;
     // the frames' wide-BVH query and its status over n host rays (rt_wide_query)
     int wide_query(const float* orig, const float* dir, int64_t n, int kind, float* o_out, float* d_out,
                    int32_t* status, int32_t* id, float* t, float* u, float* v, uint8_t* shadow);
@@ -310,10 +320,21 @@ private:
     // level 1 around the launch's shading pass: its frame buffer and zeroed count, then the count and refl_level
     int refl_level1_begin(const KParams& P, hipStream_t stream);
     int refl_level1_finish(const KParams& P, hipStream_t stream, const char* what, bool run_empty);
-    // frames in flight (render_bands_device): make 'stream' wait for every live slot's last
-    // launch, or the host for all of them (before buffers that launches read are replaced)
+    // frames in flight (render_bands_device) and ray queries in flight on the callers' streams: make
+    // 'stream' wait for every live slot's last launch and the last query, or the host for all of them
+    // (before buffers that launches read are replaced)
     int wait_slots(hipStream_t stream);
     int sync_slots();
+    // The device ray queries (trace_rays_device, is_shadowed_device).  query_fence_ follows the last launch
+    // on any stream: fence_stream_ runs in order, so the last record() comes after every earlier one.
+    Fence query_fence_;
+    int64_t query_calls_[2] = {}, query_rays_[2] = {};   // closest hit, shadow
+    // before a query launch on 'stream': the count and the pointers (n_required of them must not be null when
+    // n > 0; each must be memory of device_), the scene as a frame brings it up to date, P with its risk words
+    int begin_ray_query(const char* what, const void* const* ptrs, int nptrs, int n_required, int64_t n,
+                        hipStream_t stream, KParams& P);
+    // after it: the fence and the counters (kind 0 closest hit, 1 shadow)
+    int end_ray_query(int kind, int64_t n, hipStream_t stream);
 
     Knobs knobs_;
     int device_;

@@ -117,26 +117,32 @@ void TriGeometry::copy_host_from(const TriGeometry& lead)
 }
 
 // (A pointer the runtime does not know leaves a sticky error behind: cleared.)
-int TriGeometry::check_input(const void* d_verts, const void* d_idx, std::string& err)
+int check_device_pointers(const void* const* ptrs, int count, int device, const char* what, std::string& err)
 {
-    for (const void* p : {d_verts, d_idx}) {
-        if (!p)
+    for (int i = 0; i < count; i++) {
+        if (!ptrs[i])
             continue;
         hipPointerAttribute_t a{};
         const char* bad = nullptr;
-        if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        if (hipPointerGetAttributes(&a, ptrs[i]) != hipSuccess) {
             (void)hipGetLastError();
-            bad = "geometry input: not a device pointer";
+            bad = ": not a device pointer";
         } else if (a.type != hipMemoryTypeDevice)
-            bad = "geometry input: not device memory";
-        else if (a.device != device_)
-            bad = "geometry input: memory of another device";
+            bad = ": not device memory";
+        else if (a.device != device)
+            bad = ": memory of another device";
         if (bad) {
-            err = bad;
+            err = std::string(what) + bad;
             return RT_EINVAL;
         }
     }
     return RT_OK;
+}
+
+int TriGeometry::check_input(const void* d_verts, const void* d_idx, std::string& err)
+{
+    const void* const ptrs[] = {d_verts, d_idx};
+    return check_device_pointers(ptrs, 2, device_, "geometry input", err);
 }
 
 int TriGeometry::ingest(const float* d_verts, int64_t nv, const int32_t* d_idx, int64_t n, hipStream_t stream,

@@ -21,6 +21,11 @@
 
 namespace rt {
 
+// Every non-null pointer of the list is device memory of 'device' (hipPointerGetAttributes on the address
+// given: the range behind it is the caller's word), else RT_EINVAL with "<what>: ..." in err.  The check of
+// the geometry input and of the device ray queries.
+int check_device_pointers(const void* const* ptrs, int count, int device, const char* what, std::string& err);
+
 class TriGeometry {
 public:
     ~TriGeometry();

@@ -417,6 +417,62 @@ class Renderer:
                    ptr(v, _f32p), ptr(ret, _u8p))
         return ids, t, u, v, ret
 
+    # -- ray queries on GPU memory (include/rt_mi355x.h "Ray queries on device memory") --------
+    _RAY_OUT = (("tri_id", "int32"), ("t", "float32"), ("u", "float32"), ("v", "float32"), ("ret", "uint8"))
+
+    def _ray_stream(self, stream):
+        import torch
+        return torch.cuda.current_stream(self.device) if stream is None else stream
+
+    def trace_rays_device(self, orig, dirs, out=None, counts=None, stream=None):
+        """rt_trace_rays_device: trace_rays for rays in GPU memory, through the frames' wide-BVH query, in
+        the order of ``stream`` (a torch stream; default the current one) and without a host wait
+        -> dict(tri_id int32, t, u, v float32, ret uint8) of torch tensors [n], bit for bit trace_rays'
+        answers.  orig, dirs: contiguous float32 [n, 3] tensors on this renderer's GPU.  out: such a dict to
+        write into (tensors of at least n elements; the rest is left alone), else new tensors.  counts: an
+        int64 [2] tensor the kernel adds to: [0] rays the certified wide query answered, [1] rays traced
+        through the octree (or the brute-force loop)."""
+        import torch
+        op, dp, n = _lib.device_ray_args(orig, dirs, self.device, ("orig", "dirs"))
+        if n > 1 << 30:
+            raise ValueError(f"trace_rays_device: {n} rays, at most 2^30 are taken")
+        stream = self._ray_stream(stream)
+        if out is None:
+            with torch.cuda.stream(stream):
+                out = {k: torch.empty(n, dtype=getattr(torch, dt), device=orig.device) for k, dt in self._RAY_OUT}
+        ptrs = [_lib.device_ray_out(out[k], k, getattr(torch, dt), n, self.device) for k, dt in self._RAY_OUT]
+        cp = None if counts is None else _lib.device_ray_out(counts, "counts", torch.int64, 2, self.device)
+        self._call("rt_trace_rays_device", C.c_void_p(op), C.c_void_p(dp), n, *[C.c_void_p(p) for p in ptrs],
+                   C.c_void_p(cp), self._stream_ptr(stream, self.device))
+        return out
+
+    def is_shadowed_device(self, points, normals, light=None, out=None, stream=None):
+        """rt_is_shadowed_device: Renderer::is_shadowed(point, normal, light) for (point, normal) pairs in GPU
+        memory -> a uint8 torch tensor [n], 1 where the point is shadowed (all 0 with compute_shadows off).
+        points, normals, stream as in trace_rays_device; light: 3 floats, None = the scene's light; out: a
+        uint8 tensor of at least n elements to write into."""
+        import torch
+        pp, np_, n = _lib.device_ray_args(points, normals, self.device, ("points", "normals"))
+        if n > 1 << 30:
+            raise ValueError(f"is_shadowed_device: {n} pairs, at most 2^30 are taken")
+        stream = self._ray_stream(stream)
+        if out is None:
+            with torch.cuda.stream(stream):
+                out = torch.empty(n, dtype=torch.uint8, device=points.device)
+        sp = _lib.device_ray_out(out, "out", torch.uint8, n, self.device)
+        lp = None if light is None else f32(light).reshape(3)
+        self._call("rt_is_shadowed_device", C.c_void_p(pp), C.c_void_p(np_), n, ptr(lp, _f32p), C.c_void_p(sp),
+                   self._stream_ptr(stream, self.device))
+        return out
+
+    def device_ray_queries(self):
+        """rt_get_device_ray_queries -> (calls, rays): launches of the closest-hit and the shadow kernel
+        since the renderer was created, and the rays given to them (two ints each)."""
+        calls, rays = np.zeros(2, np.int64), np.zeros(2, np.int64)
+        i64p = C.POINTER(C.c_int64)
+        self._call("rt_get_device_ray_queries", ptr(calls, i64p), ptr(rays, i64p))
+        return (int(calls[0]), int(calls[1])), (int(rays[0]), int(rays[1]))
+
     def wide_query(self, orig, dirs, kind=1):
         """rt_wide_query: the frames' wide-BVH query on the GPU with its status -> dict(o, d, status,
         id, t, u, v, shadowed); kind 0 plain rays, 1 camera rays, 2 (hit point, normal) pairs as

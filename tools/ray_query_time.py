@@ -1,0 +1,166 @@
+"""Closest-hit and shadow queries for rays that lie in GPU memory, on the C4 scene (sphere1m, default BVH
+settings) after rt_finish_accel, 2^22 rays per set, made on the GPU from a seed:
+  a  camera rays: from the camera position through uniformly random points of the 1920 x 1080 frame
+  b  uniformly random origins in the scene's box, uniformly random directions
+  c  shadow pairs: the hit points of (a) with their triangles' geometric normals (towards the camera)
+Rows, all in one process:
+  host           Renderer.trace_rays from numpy arrays (the copy to numpy is outside the timed part; the
+                 upload, the download and the host wait are inside it: they are part of that call)
+  device_octree  trace_rays_device / is_shadowed_device of a second renderer created with RT_WBVH=0
+  device         the same calls of the default renderer
+Each call is timed with a torch.cuda.Event pair on the call's stream, after a warm-up of the same shape;
+the median and the range of the repetitions are reported, with Mrays/s from the median and the counts
+trace_rays_device adds up (rays answered by the wide query, rays traced through the octree).  The outputs
+of all rows of one set must be equal bit for bit, else the tool exits with status 1.  Rows whose calls the
+loaded library lacks are skipped (RT_LIB_PATH naming an older build: the host row alone).
+Usage: python tools/ray_query_time.py [repetitions [log2 rays]]"""
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from raytracercpp_amd import _lib, scenes
+from raytracercpp_amd.renderer import Renderer, render
+
+reps = max(10, int(sys.argv[1])) if len(sys.argv) > 1 else 10
+n = 1 << (int(sys.argv[2]) if len(sys.argv) > 2 else 22)
+KEYS = ("tri_id", "t", "u", "v", "ret")
+dev = torch.device("cuda", 0)   # (no GPU: this raises at the first tensor)
+gen = torch.Generator(device=dev)
+gen.manual_seed(20261020)
+sc, st = scenes.sphere1m()
+
+
+def unit(v):
+    return v / v.norm(dim=1, keepdim=True)
+
+
+def rays_camera():
+    ndc = torch.rand((n, 2), generator=gen, device=dev) * 2.0 - 1.0
+    p = torch.cat([ndc, -torch.ones((n, 1), device=dev), torch.ones((n, 1), device=dev)], 1)
+    pinv = torch.from_numpy(np.asarray(sc.proj_inv, np.float32).reshape(4, 4)).to(dev)
+    c2w = torch.from_numpy(np.asarray(sc.cam_to_world, np.float32).reshape(4, 4)).to(dev)
+    q = p @ pinv.T
+    q = (q / q[:, 3:]) @ c2w.T
+    cam = torch.from_numpy(np.asarray(sc.cam_pos, np.float32)).to(dev)
+    d = unit(q[:, :3] / q[:, 3:] - cam)
+    return cam.repeat(n, 1).contiguous(), d.contiguous()
+
+
+def rays_box():
+    v = torch.from_numpy(sc.tri.reshape(-1, 3)).to(dev)
+    lo, hi = v.min(0).values, v.max(0).values
+    o = lo + (hi - lo) * torch.rand((n, 3), generator=gen, device=dev)
+    d = unit(torch.randn((n, 3), generator=gen, device=dev))
+    return o.contiguous(), d.contiguous()
+
+
+def shadow_pairs(o, d, out):
+    hit = out["ret"] != 0
+    tri = torch.from_numpy(sc.tri.reshape(-1, 3, 3)).to(dev)[out["tri_id"][hit].long()]
+    nrm = unit(torch.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0], dim=1))
+    nrm = torch.where(((nrm * d[hit]).sum(1, keepdim=True) > 0), -nrm, nrm)
+    ok = torch.isfinite(nrm).all(1)   # (the sphere's zero-area pole triangles have no normal)
+    p = (o[hit] + d[hit] * out["t"][hit][:, None])[ok]
+    return p.contiguous(), nrm[ok].contiguous()
+
+
+def timed(call):
+    """The call's results and its durations in ms (one warm-up, then `reps` repetitions between event pairs)."""
+    res = call()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        res = call()
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return res, ms
+
+
+def report(ray_set, row, count, ms, counts=None):
+    med = statistics.median(ms)
+    line = {"set": ray_set, "row": row, "rays": count, "ms_median": round(med, 4), "ms_min": round(min(ms), 4),
+            "ms_max": round(max(ms), 4), "reps": len(ms), "mrays_per_s": round(count / med / 1e3, 1)}
+    if counts is not None:
+        line["counts"] = counts
+    print(json.dumps(line), flush=True)
+    return line
+
+
+def make(env=None):
+    old = {k: os.environ.get(k) for k in (env or {})}
+    os.environ.update(env or {})
+    try:
+        r = Renderer(0)
+    finally:
+        for k, v in old.items():
+            os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
+    r.load_scene(sc, st)
+    render(r)
+    r.finish_accel()
+    render(r)
+    return r
+
+
+def as_bits(t):
+    return t.view(torch.int32) if t.dtype == torch.float32 else t
+
+
+have = all(_lib.has(s) for s in _lib.RAY_QUERIES) if hasattr(_lib, "RAY_QUERIES") else False
+if not have:
+    print("device, device_octree: skipped (the library lacks the device ray queries)", flush=True)
+renderers = {"device": make()}
+if have:
+    renderers["device_octree"] = make({"RT_WBVH": "0"})
+print(json.dumps({"scene": "sphere1m", "triangles": int(sc.ntri), "rays_per_set": n, "repetitions": reps,
+                  "wide_tree": {k: r.stats()["wide_tree"] for k, r in renderers.items()}}), flush=True)
+
+ok = True
+lines = []
+pairs = None
+for ray_set, maker in (("a", rays_camera), ("b", rays_box)):
+    o, d = maker()
+    oh, dh = o.cpu().numpy(), d.cpu().numpy()
+    torch.cuda.synchronize()
+    ref, ms = timed(lambda: renderers["device"].trace_rays(oh, dh))
+    lines.append(report(ray_set, "host", n, ms))
+    ref = [torch.from_numpy(a).to(dev) for a in ref]
+    for row in ("device_octree", "device"):
+        if not have:
+            continue
+        r = renderers[row]
+        out = {k: torch.empty(n, dtype=a.dtype, device=dev) for k, a in zip(KEYS, ref)}
+        counts = torch.zeros(2, dtype=torch.int64, device=dev)
+        _, ms = timed(lambda: r.trace_rays_device(o, d, out=out, counts=counts))
+        c = [int(x) // (reps + 1) for x in counts.cpu()]
+        lines.append(report(ray_set, row, n, ms, c))
+        for k, a in zip(KEYS, ref):
+            if not torch.equal(as_bits(out[k]), as_bits(a)):
+                ok = False
+                print(f"set {ray_set}, row {row}: {k} differs from the host row in "
+                      f"{int((as_bits(out[k]) != as_bits(a)).sum())} rays", flush=True)
+        if ray_set == "a" and row == "device":
+            pairs = shadow_pairs(o, d, out)
+if pairs is not None:
+    p, nrm = pairs
+    first = None
+    for row in ("device_octree", "device"):
+        sh, ms = timed(lambda: renderers[row].is_shadowed_device(p, nrm))
+        lines.append(report("c", row, int(p.shape[0]), ms))
+        print(json.dumps({"set": "c", "row": row, "shadowed": int(sh.sum())}), flush=True)
+        if first is None:
+            first = sh.clone()
+        elif not torch.equal(first, sh):
+            ok = False
+            print(f"set c: the rows differ in {int((first != sh).sum())} pairs", flush=True)
+for r in renderers.values():
+    r.close()
+print(json.dumps({"equal": ok}), flush=True)
+sys.exit(0 if ok else 1)
