@@ -500,6 +500,15 @@ int rt_tile_mask(rt_renderer *r, int32_t src, uint32_t *words, int64_t cap, int3
  * (0: every set is the root's).  sets may be NULL (info only); cap: its size in words (4 per block).
  * RT_ESTATE before the first frame launch */
 int rt_tile_starts(rt_renderer *r, int32_t src, uint32_t *sets, int64_t cap, int32_t info[3]);
+/* the tile lists of the last frame launch (with its tile mask; RT_TILE_LIST=0: none): the launch's 8 x 8 tiles
+ * (row-major over its local rows, info[0] per row) that the frame kernel's queue handed out ('covered': a lane
+ * of the tile lies in a block whose mask bit is set) and those its waves filled with the background at their
+ * exit ('clear'), each in ascending order; tiles without a pixel on the image are in neither.  src 0: as the
+ * device computed them; 1: recomputed on the host from the mask words read back.  info: tiles per row, tile
+ * rows, covered tiles, clear tiles, 1 when the launch used lists (0: none, both counts 0).  tiles receives the
+ * covered tiles, then the clear ones; it may be NULL (info only); cap: its size in words.  RT_ESTATE before the
+ * first frame launch */
+int rt_tile_lists(rt_renderer *r, int32_t src, int32_t *tiles, int64_t cap, int32_t info[5]);
 
 /* ---- tp2/src/mat.cpp restated (host) ---- */
 /* kind: 0 Translation(x,y,z) 1 RotationX(x deg) 2 RotationY 3 RotationZ 4 Scale(x,y,z) 5 Identity */

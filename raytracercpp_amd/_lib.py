@@ -151,6 +151,7 @@ SIGNATURES = {
     "rt_band_counters": (C.c_int, [_H, _i64p, _i64p]),
     "rt_tile_mask": (C.c_int, [_H, C.c_int32, _u32p, C.c_int64, _i32p]),
     "rt_tile_starts": (C.c_int, [_H, C.c_int32, _u32p, C.c_int64, _i32p]),
+    "rt_tile_lists": (C.c_int, [_H, C.c_int32, _i32p, C.c_int64, _i32p]),
     "rt_make_transform": (None, [C.c_int32, C.c_float, C.c_float, C.c_float, _f32p]),
     "rt_compose": (None, [_f32p, _f32p, _f32p]),
     "rt_inverse": (None, [_f32p, _f32p]),
@@ -190,6 +191,8 @@ GEOMETRY_INPUT = ("rt_set_triangles_device", "rt_update_vertices_device", "rt_ge
                   "rt_gather_triangles_device", "rt_set_accel_deferred", "rt_get_accel_builds")
 # the device ray queries, likewise (tools/ray_query_time.py skips their rows for such a library)
 RAY_QUERIES = ("rt_trace_rays_device", "rt_is_shadowed_device", "rt_get_device_ray_queries")
+# the tile lists' read-back, likewise (an A/B run against the parent commit's library)
+TILE_LISTS = ("rt_tile_lists",)
 
 _lib = None
 
@@ -214,7 +217,7 @@ def lib():
             pass
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            if name in GEOMETRY_INPUT + RAY_QUERIES and os.environ.get("RT_LIB_PATH") and not hasattr(L, name):
+            if name in GEOMETRY_INPUT + RAY_QUERIES + TILE_LISTS and os.environ.get("RT_LIB_PATH") and not hasattr(L, name):
                 continue
             fn = getattr(L, name)
             fn.restype = res

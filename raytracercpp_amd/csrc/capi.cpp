@@ -510,6 +510,10 @@ int rt_tile_starts(rt_renderer* r, int32_t src, uint32_t* sets, int64_t cap, int
 {
     return guarded(R(r), [&] { return info ? R(r)->tile_starts(src, sets, cap, info) : RT_EINVAL; });
 }
+int rt_tile_lists(rt_renderer* r, int32_t src, int32_t* tiles, int64_t cap, int32_t info[5])
+{
+    return guarded(R(r), [&] { return info ? R(r)->tile_lists(src, tiles, cap, info) : RT_EINVAL; });
+}
 int rt_band_counters(rt_renderer* r, int64_t* shadow_rays, int64_t* reflection_rays)
 {
     return guarded(R(r), [&] {

@@ -49,6 +49,7 @@ __device__ __forceinline__ void w_step_hook(uint32_t cur, int leaf)
 #include "kparams.hpp"
 #include "rt_math.hpp"
 #include "wbvh.hpp"
+#include "tile_lists.hpp"
 #include "launch.hpp"
 
 namespace rt {
@@ -859,16 +860,19 @@ __device__ void parallax_occlusion_mapping(const KParams& P, int tri, float u, f
 }
 
 #if RT_PHASE_TIME
-// per wave: [0..6] cycles per phase, [7] the last mark (LDS; the wave's first active lane updates)
-__shared__ unsigned long long g_phase[WAVES_PER_BLOCK][8];
+// per wave: [0..7] cycles per phase ([7]: the tiles the mask answers, in the tile loop and in the exit fill), [8] the
+// last mark (LDS; the wave's first active lane updates)
+constexpr int PH_PHASES = 8;
+static_assert(PH_PHASES <= DBG_WORDS, "a wave's record holds its phases");
+__shared__ unsigned long long g_phase[WAVES_PER_BLOCK][PH_PHASES + 1];
 __device__ __forceinline__ void ph_mark(int k)
 {
     const unsigned long long now = __builtin_amdgcn_s_memtime();
     const uint64_t act = __ballot(1);
     if ((int)__lane_id() == __ffsll((unsigned long long)act) - 1) {
         const int w = threadIdx.x >> 6;
-        g_phase[w][k] += now - g_phase[w][7];
-        g_phase[w][7] = now;
+        g_phase[w][k] += now - g_phase[w][PH_PHASES];
+        g_phase[w][PH_PHASES] = now;
     }
 }
 #define PH_MARK(k) ph_mark(k)
@@ -1788,12 +1792,40 @@ constexpr int BQ_BATCH = 4;   // tickets per block dequeue (<= 255)
 // against alternatives (r02): guided chunks of 2-4 adjacent tiles per wave dequeue, tickets
 // taken one tile ahead, blocked orders (patches of 8x8 .. 32x16 tiles), 2x2 tile quads per
 // block batch and 8-ticket block batches were all slower.
+// LIST (the plain kernel over the wide BVH, with KParams::list_off): the shards divide the launch's covered
+// tiles instead (tile_lists.hpp tile_shard_range), and a ticket names an entry of that list.
+__device__ __forceinline__ const int32_t* tile_lists_of(const KParams& P)
+{
+    return reinterpret_cast<const int32_t*>(P.tile_mask) + P.list_off;
+}
+
+// whether ticket t of shard s names a tile
+template <bool LIST>
+__device__ __forceinline__ bool shard_has(const KParams& P, int s, int t);
+
+template <bool LIST = false>
 __device__ __forceinline__ int shard_tile(const KParams& P, int s, int t)
 {
+    if (LIST && P.list_off) {
+        const int32_t* tl = tile_lists_of(P);
+        int r0, r1;
+        tile_shard_range(ldg(tl), s, TILE_SHARDS, r0, r1);
+        return t < r1 - r0 ? ldg(tl + TL_HEAD + r0 + t) : -1;
+    }
     const int r0 = (int)((long long)P.tiles_y * s / TILE_SHARDS), r1 = (int)((long long)P.tiles_y * (s + 1) / TILE_SHARDS);
     return t < (r1 - r0) * P.tiles_x ? r0 * P.tiles_x + t : -1;
 }
 
+template <bool LIST>
+__device__ __forceinline__ bool shard_has(const KParams& P, int s, int t)
+{
+    if (LIST && P.list_off) {
+        int r0, r1;
+        tile_shard_range(ldg(tile_lists_of(P)), s, TILE_SHARDS, r0, r1);
+        return t < r1 - r0;
+    }
+    return shard_tile(P, s, t) >= 0;
+}
 
 // Block-shared dequeue.  One global atomic takes WAVES_PER_BLOCK consecutive tickets of the
 // block's shard, and the block's waves hand them out among themselves through one LDS word
@@ -1855,6 +1887,7 @@ __device__ __forceinline__ void tile_stats_flush(const KParams& P, int lane)
     if (m) atomicMax(P.tile_stats + 1, (unsigned long long)m);
 }
 
+template <bool LIST = false>
 __device__ __forceinline__ int tile_queue_next_shards(const KParams& P)
 {
     const int lane = threadIdx.x & 63;
@@ -1868,7 +1901,7 @@ __device__ __forceinline__ int tile_queue_next_shards(const KParams& P)
         const unsigned int g = (w >> 24) & 0x7fu, c = (w >> 16) & 0xffu, i = w & 0xffffu;
         if (i < c) {
             const int slot = (int)(g & 3u);
-            return shard_tile(P, g_bq.sh[slot], g_bq.base[slot] + (int)i);
+            return shard_tile<LIST>(P, g_bq.sh[slot], g_bq.base[slot] + (int)i);
         }
         if (i == c) {
             // this wave refills: WAVES_PER_BLOCK tickets of the first non-empty shard
@@ -1880,7 +1913,7 @@ __device__ __forceinline__ int tile_queue_next_shards(const KParams& P)
                                        (unsigned)BQ_BATCH);
                 b = __builtin_amdgcn_readfirstlane(t);
                 n = 0;
-                while (n < BQ_BATCH && shard_tile(P, shard, b + n) >= 0)
+                while (n < BQ_BATCH && shard_has<LIST>(P, shard, b + n))
                     n++;
                 if (n > 0)
                     break;
@@ -1897,7 +1930,7 @@ __device__ __forceinline__ int tile_queue_next_shards(const KParams& P)
                 __hip_atomic_store(&g_bq.word, n > 0 ? (g1 << 24) | ((unsigned)n << 16) | 1u : 0x80000000u,
                                    __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
-            return n > 0 ? shard_tile(P, shard, b) : -1;
+            return n > 0 ? shard_tile<LIST>(P, shard, b) : -1;
         }
         // another wave is taking the next batch
         for (;;) {
@@ -1915,6 +1948,7 @@ __device__ __forceinline__ int tile_queue_next_shards(const KParams& P)
 // The next tile: first the heavy list (one global ticket per tile), then the sharded queue with the
 // heavy tiles skipped (each tile exactly once; the split tiles of heavy_prep_kernel are
 // trace_split_part's).
+template <bool LIST = false>
 __device__ __forceinline__ int tile_queue_next(const KParams& P)
 {
     const int lane = threadIdx.x & 63;
@@ -1931,12 +1965,12 @@ __device__ __forceinline__ int tile_queue_next(const KParams& P)
                 __hip_atomic_store(&g_bq.heavy_done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         for (;;) {
-            const int tile = tile_queue_next_shards(P);
+            const int tile = tile_queue_next_shards<LIST>(P);
             if (tile < 0 || !((ldg(P.heavy_bits + (tile >> 5)) >> (tile & 31)) & 1u))
                 return tile;
         }
     }
-    return tile_queue_next_shards(P);
+    return tile_queue_next_shards<LIST>(P);
 }
 
 // The wave's instruction-issue priority among the waves of its SIMD: heavy-list tiles carry a level
@@ -2106,6 +2140,72 @@ __device__ __noinline__ void fill_masked_tile(const KParams& P, int lr, int px)
 #endif
 }
 
+// The exit fill (KParams::list_off): a wave that has found the queue exhausted writes its static
+// share of the launch's clear tiles, step k of wave w (of the grid's W) the entries [(w + k W) T, + T) of the
+// list -- no ticket, no atomic.  Entries whose heavy bit is set are skipped: the heavy or the split list named
+// them and the tile loop wrote them (its mask test fills a listed tile that has become clear).  So every
+// on-image tile of a launch is written exactly once: by a split part, a heavy ticket, a shard ticket over
+// 'covered' (heavy bit clear) or here (clear, heavy bit clear).  (A launch of its own for the fill, ahead of the
+// frame or behind it, was measured and lost: DESIGN.md 5.14.)
+//   packed (only ds_out requested: the band launches with fused SSAA): a lane writes one output pixel, the word
+//   fill_masked_tile writes; T = 64 / (output pixels per tile) tiles per step;
+//   any other output set: T = 1, the tile's on-image lanes through fill_masked_tile.
+// Each tile's cost is the step's cycles / the step's tiles, at least 1 (every on-image tile's cost is above 0).
+__device__ __noinline__ void fill_clear_tiles(const KParams& P)
+{
+    const int lane = threadIdx.x & 63;
+    const int32_t* tl = tile_lists_of(P);
+    const int nclear = ldg(tl + 1);
+    const int32_t* clear = tl + TL_HEAD + P.tiles_x * P.tiles_y;
+    const long long w = (long long)blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6), W = (long long)gridDim.x * WAVES_PER_BLOCK;
+    const bool packed = P.ds_out && !P.argb && !P.rgba && !P.hit_id && !P.hit_t && !P.shadow;
+    const int sh = packed ? P.ds_shift : 0;
+    const int q = packed ? 64 >> (2 * sh) : 64;   // lanes per tile: its output pixels (packed), its pixels
+    const int T = 64 / q;                         // tiles per step
+    const int k = lane / q, j = lane % q;         // the lane's tile of the step and its pixel there
+    const uint32_t c = color_to_argb(background());
+    const uint32_t word = qrgb((int)((c >> 16) & 0xffu), (int)((c >> 8) & 0xffu), (int)(c & 0xffu));
+    for (long long e0 = w * T; e0 < nclear; e0 += W * T) {
+        const uint64_t t0 = P.tile_cost ? __builtin_amdgcn_s_memtime() : 0ull;
+        int tile = -1;
+        if (e0 + k < nclear) {
+            tile = ldg(clear + (e0 + k));
+            if (P.heavy_bits && ((ldg(P.heavy_bits + (tile >> 5)) >> (tile & 31)) & 1u))
+                tile = -1;
+        }
+        if (tile >= 0) {
+            int tx, ty;
+            tile_xy(P, tile, tx, ty);
+            const int side = 8 >> sh;   // (output) pixels per tile side
+            const int px = tx * 8 + ((j % side) << sh);
+            const int lr = ty * 8 + ((j / side) << sh);
+            const int py = lr < P.local_rows ? global_row(P, lr) : P.rh;
+            if (px < P.rw && py < P.rh) {
+                if (packed)
+                    P.ds_out[(size_t)(lr >> sh) * (size_t)(P.rw >> sh) + (size_t)(px >> sh)] = word;
+                else
+                    fill_masked_tile(P, lr, px);
+            }
+        }
+        const uint64_t firsts = __ballot(tile >= 0 && j == 0);
+        const int n = __popcll(firsts);
+        if (n == 0)
+            continue;
+#if RT_COUNT
+        if (packed && P.counters && lane == __ffsll((unsigned long long)firsts) - 1)
+            atomicAdd(&P.counters[28], (unsigned long long)n);   // (fill_masked_tile counts its own)
+#endif
+        if (P.tile_cost) {
+            const uint64_t cy = (__builtin_amdgcn_s_memtime() - t0) / (uint64_t)n;
+            const uint32_t c32 = cy > 0xFFFFFFFFull ? 0xFFFFFFFFu : cy < 1 ? 1u : (uint32_t)cy;
+            if (tile >= 0 && j == 0) {
+                P.tile_cost[tile] = c32;
+                tile_stats_add(c32, c32);
+            }
+        }
+    }
+}
+
 // Renderer::ray_trace (renderer.cpp:1068-1116): one lane per pixel, one wave
 // per 8x8 tile.  Waves are persistent and pull tiles from the sharded device-scope
 // queue (tile_queue_next): shadow-ray-heavy tiles cluster around the object, so
@@ -2115,107 +2215,21 @@ __device__ __noinline__ void fill_masked_tile(const KParams& P, int lr, int px)
 // KParams::plain): those code paths are compiled out.
 // OCT (with PLAIN): frames before the wide BVH is resident -- the octree walk in line, no
 // wide-BVH code, at its own occupancy
+// LIST (ray_trace_list_kernel, with PLAIN over the wide BVH and KParams::list_off): the queue runs
+// over the launch's covered tiles and the waves fill the clear ones at their exit.  A kernel of its own, chosen per
+// launch: ray_trace_kernel's instances carry no trace of the lists and compile to the code they had without them.
+// The two kernels share their text, ray_trace_body.hpp (a function template for it changed every instance's code).
 template <bool REFL, bool PLAIN = false, bool OCT = false>
 __global__ __launch_bounds__(BLOCK, OCT ? RT_OCC_OCT : PLAIN ? RT_OCC_PLAIN : RT_OCC) void ray_trace_kernel(KParams P_arg)
 {
-    // The kernel reads its parameters where the kernel received them, through a pointer
-    // the compiler cannot hoist out of the tile loop: each field is loaded (scalar cache) where
-    // a tile uses it instead of ~100 of them being held in registers across the loop, which
-    // spilled (register budget).
-    auto kp = __builtin_amdgcn_kernarg_segment_ptr();
-    (void)P_arg;
-    const KParams& P = *reinterpret_cast<const KParams*>((const void*)kp);
-    uint2* lv = lane_stack();
-    int lane = threadIdx.x & 63;
-    unsigned nshadow = 0, nrefl = 0;
-    tile_queue_init();
-#if RT_PHASE_TIME
-    if (PLAIN && lane == 0) {
-        for (int k = 0; k < 7; k++)
-            g_phase[threadIdx.x >> 6][k] = 0;
-        g_phase[threadIdx.x >> 6][7] = __builtin_amdgcn_s_memtime();
-    }
-#endif
-    for (;;) {
-        auto kpl = kp;
-        asm volatile("" : "+s"(kpl));   // (the loop's loads depend on it: not hoisted)
-        const KParams& P = *reinterpret_cast<const KParams*>((const void*)kpl);
-        const v3 cam = mk(P.cam_pos[0], P.cam_pos[1], P.cam_pos[2]);
-        if (PLAIN && !REFL && !OCT && P.heavy_group == SPLIT_G &&
-            !__builtin_amdgcn_readfirstlane(__hip_atomic_load(&g_bq.split_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))) {
-            // the split tiles' parts first (trace_split_part)
-            int t = 0;
-            if (lane == 0)
-                t = atomicAdd(P.heavy_ctr + 2, 1);
-            t = __builtin_amdgcn_readfirstlane(t);
-            if (t < P.split_parts * min(ldg(P.heavy_ctr + 3), P.tiles_x * P.tiles_y / 16)) {
-                trace_split_part<SPLIT_G>(P, lv, t, lane, nshadow);
-                continue;
-            }
-            if (lane == 0)
-                __hip_atomic_store(&g_bq.split_done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-        const int tq = tile_queue_next(P);
-        if (PLAIN) PH_MARK(6);
-        if (tq < 0)
-            break;
-        const int tile = tq & 0x0fffffff;
-        if (P.heavy_list)
-            set_wave_prio(tq >> 28);
-        const uint64_t tile_t0 = __builtin_amdgcn_s_memtime();
-        int tx, ty;
-        tile_xy(P, tile, tx, ty);
-        int px = tx * 8 + (lane & 7);
-        int lr = ty * 8 + (lane >> 3);
-        int py = lr < P.local_rows ? global_row(P, lr) : P.rh;
-        if (PLAIN) PH_MARK(0);
-        if (px >= P.rw || py >= P.rh) {
-            if (P.tile_cost && lane == 0)
-                P.tile_cost[tile] = 0u;
-            continue;
-        }
-        if (PLAIN && !REFL && !OCT && P.tile_mask) {
-            // the tile mask: no ray of a block whose bit is clear enters the cut, so each
-            // is a certified miss; a tile whose lanes' blocks are all clear is the background's
-            const uint32_t mw = ldg(P.tile_mask + (size_t)(py >> 3) * (size_t)P.mask_wpr + (size_t)(px >> 8));
-            if (!__ballot((mw >> ((px >> 3) & 31)) & 1u)) {
-                fill_masked_tile(P, lr, px);
-                if (P.tile_cost)
-                    tile_cost_store(P, tile, tile_t0, lane);
-                continue;
-            }
-        }
-        // ray generation, renderer.cpp:1086-1098
-        const v3 rd = camera_dir(P, px, py, cam);
-        if (PLAIN) PH_MARK(1);
+    constexpr bool LIST = false;
+#include "ray_trace_body.hpp"
+}
 
-        uint32_t rng = REFL ? pixel_seed((uint32_t)(py * P.rw + px), P.rng_seed) : 0u;
-        PixelOut po = trace_pixel<REFL, PLAIN, 1, OCT>(P, cam, rd, lv, rng, nshadow, nrefl,
-                                                        PLAIN && !REFL && !OCT ? tile_start_index(P, px, py) : -1);
-        size_t o = (size_t)lr * P.rw + px;
-        if (P.argb) P.argb[o] = color_to_argb(po.color);
-        if (!REFL && P.ds_out) downscale_tile(P, lane, lr, px, color_to_argb(po.color));
-        if (P.rgba) P.rgba[o] = make_float4(po.color.r, po.color.g, po.color.b, po.alpha);
-        if (P.hit_id) P.hit_id[o] = po.found ? po.src : -1;
-        if (P.hit_t) P.hit_t[o] = po.fin.t;
-        if (P.shadow) P.shadow[o] = (uint8_t)(po.found && po.shadowed);
-        if (!PLAIN && P.zbuf) write_ssao_buffers(P, o, po.found, cam, rd, po.fin);
-        if (PLAIN) PH_MARK(5);
-        if (P.tile_cost)   // the tile's shader cycles (heavy-first order of the next launch)
-            tile_cost_store(P, tile, tile_t0, lane);
-    }
-    tile_stats_flush(P, lane);
-#if RT_PHASE_TIME
-    if (PLAIN) {
-        PH_MARK(0);   // the final (empty) dequeues
-        const int wid = (int)(blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6));
-        if (P.dbg && lane == 0 && wid < DBG_WAVES)
-            for (int k = 0; k < 7; k++)
-                P.dbg[DBG_WORDS * wid + k] = g_phase[threadIdx.x >> 6][k];
-    }
-#endif
-    if (nshadow) atomicAdd(&P.counters[0], (unsigned long long)nshadow);
-    if (nrefl) atomicAdd(&P.counters[1], (unsigned long long)nrefl);
+__global__ __launch_bounds__(BLOCK, RT_OCC_PLAIN) void ray_trace_list_kernel(KParams P_arg)
+{
+    constexpr bool REFL = false, PLAIN = true, OCT = false, LIST = true;
+#include "ray_trace_body.hpp"
 }
 
 // ===========================================================================
@@ -4030,7 +4044,10 @@ hipError_t rt_launch_ray_trace(const rt::KParams* P, hipStream_t stream)
             return hipGetLastError();
         }
         const int pblocks = plain_blocks(*P);
-        hipLaunchKernelGGL((rt::ray_trace_kernel<false, true>), dim3(pblocks), dim3(rt::BLOCK), lds, stream, *P);
+        if (P->list_off)   // (the launch was given tile lists: renderer.cpp prepare_mask decides)
+            hipLaunchKernelGGL(rt::ray_trace_list_kernel, dim3(pblocks), dim3(rt::BLOCK), lds, stream, *P);
+        else
+            hipLaunchKernelGGL((rt::ray_trace_kernel<false, true>), dim3(pblocks), dim3(rt::BLOCK), lds, stream, *P);
     } else
         hipLaunchKernelGGL((rt::ray_trace_kernel<false, false>), dim3(blocks), dim3(rt::BLOCK), lds, stream, *P);
     return hipGetLastError();
@@ -4171,6 +4188,76 @@ hipError_t rt_launch_wide_entry(const rt::WNode* wnodes, int nnodes, const rt::W
         return hipSuccess;
     hipLaunchKernelGGL(wide_entry_kernel, dim3((nb + 255) / 256), dim3(256), 0, stream, wnodes, nnodes, *C, words, K, fan,
                        max_depth, out);
+    return hipGetLastError();
+}
+
+// The tile lists of a launch (tile_lists.hpp), in two steps without an atomic, so that the order is the tiles':
+// one lane per tile classifies it, and a wave's two ballots are its words of the class bits ...
+__global__ __launch_bounds__(256) void tile_class_kernel(rt::TileLayout L, int ntiles, unsigned long long* cls)
+{
+    const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+    const int c = i < ntiles ? rt::tile_class(L, i) : (int)rt::TILE_OFF;
+    const uint64_t cov = __ballot(c == rt::TILE_COVERED), clr = __ballot(c == rt::TILE_CLEAR);
+    if ((threadIdx.x & 63) == 0 && i < ntiles) {
+        cls[2 * (i >> 6)] = cov;
+        cls[2 * (i >> 6) + 1] = clr;
+    }
+}
+
+// ... then a tile's place in its list is the number of set bits before its own: those of the words before the
+// block's (each block counts them itself: at most ntiles / 64 words), of the block's earlier waves, and of the
+// wave's lower lanes.  The wave of the last tile writes the two counts.
+__global__ __launch_bounds__(256) void tile_list_kernel(const unsigned long long* __restrict__ cls, int ntiles, int32_t* lists)
+{
+    __shared__ int s_cov[4], s_clr[4];
+    const int lane = (int)(threadIdx.x & 63), wv = (int)(threadIdx.x >> 6);
+    const int word0 = (int)blockIdx.x * 4, nwords = (ntiles + 63) / 64;
+    int a = 0, b = 0;
+    for (int k = (int)threadIdx.x; k < word0; k += 256) {
+        a += __popcll(cls[2 * k]);
+        b += __popcll(cls[2 * k + 1]);
+    }
+    for (int m = 32; m; m >>= 1) {
+        a += __shfl_xor(a, m);
+        b += __shfl_xor(b, m);
+    }
+    if (lane == 0) {
+        s_cov[wv] = a;
+        s_clr[wv] = b;
+    }
+    __syncthreads();
+    const int k = word0 + wv;
+    if (k >= nwords)
+        return;
+    int base_cov = s_cov[0] + s_cov[1] + s_cov[2] + s_cov[3], base_clr = s_clr[0] + s_clr[1] + s_clr[2] + s_clr[3];
+    for (int j = word0; j < k; j++) {
+        base_cov += __popcll(cls[2 * j]);
+        base_clr += __popcll(cls[2 * j + 1]);
+    }
+    const uint64_t cov = cls[2 * k], clr = cls[2 * k + 1];
+    const uint64_t below = (1ull << lane) - 1ull;
+    const int i = 64 * k + lane;
+    int32_t* covered = lists + rt::TL_HEAD;
+    int32_t* clear = covered + ntiles;
+    if ((cov >> lane) & 1ull)
+        covered[base_cov + __popcll(cov & below)] = i;
+    if ((clr >> lane) & 1ull)
+        clear[base_clr + __popcll(clr & below)] = i;
+    if (k == nwords - 1 && lane == 0) {
+        lists[0] = base_cov + __popcll(cov);
+        lists[1] = base_clr + __popcll(clr);
+    }
+}
+
+hipError_t rt_launch_tile_lists(const rt::TileLayout* L, int32_t* lists, hipStream_t stream)
+{
+    const int ntiles = L->tiles_x * L->tiles_y;
+    if (ntiles <= 0)
+        return hipSuccess;
+    unsigned long long* cls = reinterpret_cast<unsigned long long*>(lists + rt::tile_lists_class_word(ntiles));
+    const dim3 grid((unsigned)((ntiles + 255) / 256));
+    hipLaunchKernelGGL(tile_class_kernel, grid, dim3(256), 0, stream, *L, ntiles, cls);
+    hipLaunchKernelGGL(tile_list_kernel, grid, dim3(256), 0, stream, cls, ntiles, lists);
     return hipGetLastError();
 }
 

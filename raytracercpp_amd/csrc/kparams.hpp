@@ -181,6 +181,11 @@ struct KParams {
     // (local output row lr / f, width rw / f); argb is then nullptr.  nullptr: off.
     uint32_t* ds_out;
     int32_t ds_shift;         // log2(ssaa_factor)
+    // the tile lists (tile_lists.hpp; with tile_mask; 0: none): they lie behind the mask words in
+    // the same allocation, at tile_mask + list_off (4-byte words).  The plain kernel's queue then runs over
+    // 'covered' alone and its waves fill the 'clear' tiles at their exit.  (Here, in what was the struct's
+    // padding: every kernel's argument layout is the one it had without the lists.)
+    int32_t list_off;
 };
 
 // ---- SSAO (kernels.hip "Renderer::post_process_ssao_SIMD") ----

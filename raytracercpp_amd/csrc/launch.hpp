@@ -7,6 +7,7 @@
 
 #include "kparams.hpp"
 #include "ocone.hpp"
+#include "tile_lists.hpp"
 #include "wbvh.hpp"
 
 namespace rt {
@@ -71,6 +72,9 @@ RT_LAUNCH rt_launch_wide_mask(const rt::WNode* wnodes, int nnodes, const uint32_
 // the mask's words
 RT_LAUNCH rt_launch_wide_entry(const rt::WNode* wnodes, int nnodes, const rt::WMaskCam* C, const uint32_t* words, int K,
                                int fan, int max_depth, uint4* out, hipStream_t stream);
+// the tile lists of a launch (tile_lists.hpp) into lists (tile_lists_words(ntiles) words, 8-byte
+// aligned), from the camera's mask words (L->mask, L->band_map: device memory)
+RT_LAUNCH rt_launch_tile_lists(const rt::TileLayout* L, int32_t* lists, hipStream_t stream);
 RT_LAUNCH rt_launch_ocone(const rt::OConeEnt* E, const rt::GTri* tris, const uint32_t* todo, int n, const float lo[3],
                           const int32_t dim[3], double h, double r, double slack, double QS, double cos_cap,
                           uint2* cells, size_t ncells, hipStream_t stream);

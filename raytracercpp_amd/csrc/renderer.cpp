@@ -128,6 +128,7 @@ Knobs Knobs::from_env()
     k.scene_bound = flag("RT_SCENE_BOUND", k.scene_bound);
     k.tile_mask = flag("RT_TILE_MASK", k.tile_mask);
     k.tile_start = flag("RT_TILE_START", k.tile_start);
+    k.tile_list = flag("RT_TILE_LIST", k.tile_list);
     k.cut_budget = std::min((int)W_CUT_MAX, std::max((int)W_WIDTH, num("RT_TILE_MASK_CUT", k.cut_budget)));
     k.ocone = flag("RT_OCONE", k.ocone);
     k.ocone_dim = std::min(1024, std::max(1, num("RT_OCONE_DIM", k.ocone_dim)));
@@ -1854,6 +1855,7 @@ int Renderer::trace_frame()
     hipEventRecord(ev_[0], stream_);
     if ((rc = launch_frame(P, stream_)) != RT_OK) return rc;
     hipEventRecord(ev_[1], stream_);
+    if ((rc = probe_lists(P, stream_)) != RT_OK) return rc;
     unsigned long long cnt[NCOUNTERS] = {};
     if ((e = hipMemcpyAsync(cnt, d_counters_.p, sizeof(cnt), hipMemcpyDeviceToHost, stream_)) != hipSuccess)
         return hip_fail(e, "counters");
@@ -2349,7 +2351,7 @@ int Renderer::render_bands_impl(int band_rows, int rank, int nranks, const int32
         for (auto& ev : ring_)
             if ((e = hipEventCreate(&ev)) != hipSuccess) return hip_fail(e, "hipEventCreate");
     }
-    if ((rc = prepare_risk(P, stream)) != RT_OK || (rc = prepare_mask(P, stream, S.mask)) != RT_OK)
+    if ((rc = prepare_risk(P, stream)) != RT_OK || (rc = prepare_mask(P, stream, S.mask, layout_key)) != RT_OK)
         return rc;
     bool zeroed = false;   // heavy_prep_kernel clears the counter words itself (one dispatch fewer)
     bool overlapped = false;   // another band launch still in flight (frames in flight)
@@ -2367,6 +2369,7 @@ int Renderer::render_bands_impl(int band_rows, int rank, int nranks, const int32
     hipEventRecord(ring_[2 * ring_next_], stream);
     if ((rc = launch_frame(P, stream)) != RT_OK) return rc;
     hipEventRecord(ring_[2 * ring_next_ + 1], stream);
+    if ((rc = probe_lists(P, stream)) != RT_OK) return rc;
     ring_next_ = (ring_next_ + 1) % EV_RING;
     if (ring_count_ < EV_RING) ring_count_++;
     if (f > 1 && !fused && (e = rt_launch_downscale(target, P.rw, P.local_rows, f, d_out, stream)) != hipSuccess)
@@ -2468,15 +2471,18 @@ int Renderer::prepare_risk(KParams& P, hipStream_t stream)
 // render size, the light's finiteness or the cut changed since the stream's last launch -- the stream's
 // earlier launches read the old words before it, and no other stream reads them, so a moving camera keeps
 // its frames in flight.  No mask (nullptr) for anything but the plain kernel over the wide BVH with an
-// affine camera; RT_TILE_MASK=0: none.
-int Renderer::prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M)
+// affine camera; RT_TILE_MASK=0: none.  With the mask go the launch's tile lists (KParams::list_off, tile_lists.hpp,
+// DESIGN.md 5.14; layout_key: the band list's hash, as prepare_heavy's); RT_TILE_LIST=0: none.
+int Renderer::prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M, uint64_t layout_key)
 {
     P.tile_mask = nullptr;
     P.mask_wpr = 0;
     P.tile_start = nullptr;
     P.start_bw = 0;
+    P.list_off = 0;
     mask_last_ = nullptr;
     starts_last_ = false;
+    lists_last_ = false;
     mask_seen_ = true;
     if (!knobs_.tile_mask || !P.wnodes || !P.plain || P.has_reflection || P.zbuf || P.nbuf || wide_.nn <= 0 || !wide_.b_links.p ||
         s_.hybrid_rasterization_tracing)
@@ -2498,9 +2504,18 @@ int Renderer::prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M)
         cut_valid_ = true;
         cut_gen_++;
     }
+    // the tile lists (tile_lists.hpp) lie behind the words, 16-byte aligned; an allocation that
+    // has to grow for them loses its words
+    const int ntiles = P.tiles_x * P.tiles_y;
+    const size_t list_off = ((size_t)C.bh * C.wpr + 3) / 4 * 4;   // (KParams::list_off: 4-byte words, an int32_t)
+    const bool lists = knobs_.tile_list && ntiles > 0 && list_off + tile_lists_words(ntiles) <= (size_t)INT32_MAX;
+    const size_t need = lists ? (list_off + tile_lists_words(ntiles)) * 4 : (size_t)C.bh * C.wpr * 4;
+    if (need > M.words.bytes)
+        M.cut_gen = 0;
     if (M.cut_gen != cut_gen_ || std::memcmp(&C, &M.cam, sizeof C)) {
         M.cut_gen = 0;
-        if ((e = M.words.reserve((size_t)C.bh * C.wpr * 4)) != hipSuccess)
+        M.lists_valid = false;
+        if ((e = M.words.reserve(need)) != hipSuccess)
             return hip_fail(e, "hipMalloc (tile mask)");
         if ((e = cut_fence_.wait_on(stream)) != hipSuccess ||
             (e = rt_launch_wide_mask(P.wnodes, (int)wide_.nn, wide_.parent(), d_cut_.as<uint32_t>(),
@@ -2525,6 +2540,41 @@ int Renderer::prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M)
     }
     P.tile_mask = M.words.as<uint32_t>();
     P.mask_wpr = C.wpr;
+    if (M.use_gen != cut_gen_) {   // another tree: decide again
+        M.use_gen = cut_gen_;
+        M.list_use = -1;
+        M.list_launches = 0;
+        M.probe_pending = false;
+    }
+    if (M.probe_pending && hipEventQuery(M.probe.ev) == hipSuccess) {
+        // the figures of an earlier launch with lists on this stream have arrived (probe_lists)
+        M.probe_pending = false;
+        const unsigned long long sum = M.probe.host[0];
+        const int32_t nclear = reinterpret_cast<const int32_t*>(M.probe.host + 2)[1];
+        if (sum > 0 && nclear >= 0)
+            M.list_use = (unsigned long long)nclear * LIST_TICKET_CYCLES * LIST_MIN_SHARE_INV >= sum ? 1 : 0;
+    }
+    lists_slot_ = nullptr;
+    if (lists && M.list_use != 0) {
+        // rebuilt on the launching stream, behind the mask kernel, when the words or the launch's layout changed
+        uint64_t key = 1469598103934665603ull;
+        for (int64_t v : {(int64_t)P.rw, (int64_t)P.rh, (int64_t)P.local_rows, (int64_t)P.band_rows, (int64_t)P.rank,
+                          (int64_t)P.nranks, (int64_t)layout_key})
+            key = (key ^ (uint64_t)v) * 1099511628211ull;
+        if (!M.lists_valid || key != M.list_key || M.L.band_map != P.band_map) {
+            M.lists_valid = false;
+            M.L = TileLayout{P.rw, P.rh, P.local_rows, P.band_rows, P.rank, P.nranks, P.tiles_x, P.tiles_y,
+                             P.band_map, M.words.as<uint32_t>(), C.wpr};
+            if ((e = rt_launch_tile_lists(&M.L, M.words.as<int32_t>() + list_off, stream)) != hipSuccess)
+                return hip_fail(e, "tile_list_kernel");
+            M.lists_valid = true;
+            M.list_key = key;
+            M.list_off = (int32_t)list_off;
+        }
+        P.list_off = M.list_off;
+        lists_last_ = true;
+        lists_slot_ = &M;
+    }
     if (M.starts_valid) {
         P.tile_start = M.starts.as<uint4>();
         P.start_bw = C.bw;
@@ -2539,6 +2589,28 @@ int Renderer::prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M)
 // few very long tiles (grazing silhouette rays) start with the frame instead of ending
 // it.  Only the order changes; every tile is traced once.  Off for the reflection engine and the raster
 // path (their own kernels) and with RT_HEAVY_FIRST=0.
+// Behind a launch that was given lists, while the stream's use of them is undecided: the launch's tile-cost sum and
+// the lists' counts travel to pinned host words in stream order; a later prepare_mask on the stream finds them
+// there (it never waits for them) and decides.  From the stream's second such launch on (the first may be a tree's
+// first frame), one probe in flight at a time, none once decided.
+int Renderer::probe_lists(const KParams& P, hipStream_t stream)
+{
+    MaskSlot* M = lists_slot_;
+    lists_slot_ = nullptr;
+    if (!M || !P.list_off || !P.tile_stats || M->list_use >= 0 || M->probe_pending || ++M->list_launches < 2)
+        return RT_OK;
+    hipError_t e = hipSuccess;
+    if (!M->probe.host && ((e = hipHostMalloc(reinterpret_cast<void**>(&M->probe.host), 32)) != hipSuccess ||
+                           (e = hipEventCreateWithFlags(&M->probe.ev, hipEventDisableTiming)) != hipSuccess))
+        return hip_fail(e, "hipHostMalloc (list probe)");
+    if ((e = hipMemcpyAsync(M->probe.host, P.tile_stats, 16, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(M->probe.host + 2, P.tile_mask + P.list_off, 8, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+        (e = hipEventRecord(M->probe.ev, stream)) != hipSuccess)
+        return hip_fail(e, "list probe");
+    M->probe_pending = true;
+    return RT_OK;
+}
+
 int Renderer::prepare_heavy(KParams& P, TileCost& T, hipStream_t stream, uint64_t layout_key, bool* zeroed,
                             bool overlapped)
 {
@@ -3081,6 +3153,66 @@ int Renderer::tile_starts(int src, uint32_t* out, int64_t cap, int32_t info[3])
         wbvh_entry_host(nodes.data(), (int64_t)nodes.size(), C, words.data(), W_ENTRY_K, W_ENTRY_FAN, W_CUT_DEPTH, sets);
         std::memcpy(out, sets.data(), nw * 4);
     }
+    return RT_OK;
+}
+
+// The last frame launch's tile lists (rt_tile_lists): src 0 as the device computed them, src 1 recomputed on the
+// host from the device's mask words (and the launch's band list) read back.  info: tiles per row, tile rows,
+// covered tiles, clear tiles, 1 when the launch was given lists (0: none; both counts are 0).  out: the covered
+// tiles, then the clear ones.
+int Renderer::tile_lists(int src, int32_t* out, int64_t cap, int32_t info[5])
+{
+    hipSetDevice(device_);
+    if (!mask_seen_)
+        return fail(RT_ESTATE, "tile_lists: no frame launch yet");
+    if (src != 0 && src != 1)
+        return fail(RT_EINVAL, "tile_lists: src is 0 (device) or 1 (host)");
+    const bool on = mask_last_ != nullptr && lists_last_;
+    for (int i = 0; i < 5; i++)
+        info[i] = 0;
+    if (!on)
+        return RT_OK;
+    const MaskSlot& M = *mask_last_;
+    const int ntiles = M.L.tiles_x * M.L.tiles_y;
+    info[0] = M.L.tiles_x;
+    info[1] = M.L.tiles_y;
+    info[4] = 1;
+    hipError_t e = hipDeviceSynchronize();
+    std::vector<int32_t> covered, clear;
+    if (src == 0) {
+        std::vector<int32_t> all(TL_HEAD + 2 * (size_t)ntiles);
+        if (e == hipSuccess)
+            e = hipMemcpy(all.data(), M.words.as<int32_t>() + M.list_off, all.size() * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess)
+            return hip_fail(e, "tile_lists");
+        if (all[0] < 0 || all[1] < 0 || (int64_t)all[0] + all[1] > ntiles)
+            return fail(RT_ESTATE, "tile_lists: the device's counts exceed the launch's tiles");
+        covered.assign(all.begin() + TL_HEAD, all.begin() + TL_HEAD + all[0]);
+        clear.assign(all.begin() + TL_HEAD + ntiles, all.begin() + TL_HEAD + ntiles + all[1]);
+    } else {
+        std::vector<uint32_t> words((size_t)M.cam.bh * M.cam.wpr);
+        std::vector<int32_t> map;
+        TileLayout L = M.L;
+        if (e == hipSuccess)
+            e = hipMemcpy(words.data(), M.words.p, words.size() * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && L.band_map) {
+            map.resize((size_t)((L.local_rows + L.band_rows - 1) / L.band_rows));
+            e = hipMemcpy(map.data(), L.band_map, map.size() * 4, hipMemcpyDeviceToHost);
+            L.band_map = map.data();
+        }
+        if (e != hipSuccess)
+            return hip_fail(e, "tile_lists");
+        L.mask = words.data();
+        tile_lists_host(L, covered, clear);
+    }
+    info[2] = (int32_t)covered.size();
+    info[3] = (int32_t)clear.size();
+    if (!out)
+        return RT_OK;
+    if (cap < (int64_t)(covered.size() + clear.size()))
+        return fail(RT_EINVAL, "tile_lists: the buffer is too small");
+    std::copy(covered.begin(), covered.end(), out);
+    std::copy(clear.begin(), clear.end(), out + covered.size());
     return RT_OK;
 }
 

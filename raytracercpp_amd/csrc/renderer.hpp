@@ -20,6 +20,7 @@
 #include "kparams.hpp"
 #include "ocone.hpp"
 #include "octree.hpp"
+#include "tile_lists.hpp"
 #include "tri_geometry.hpp"
 #include "wbvh.hpp"
 #include "wide_layout.hpp"
@@ -145,6 +146,8 @@ struct Knobs {
                               // the scene bound, wbvh.hpp wbvh_mask_rect)
     bool tile_start = true;   // RT_TILE_START=0: no entry sets (every camera ray starts its wide query at the root,
                               // wbvh.hpp wbvh_entry_block); no mask, no entry sets
+    bool tile_list = true;    // RT_TILE_LIST=0: no tile lists (the queue hands out every tile and the masked ones are
+                              // filled there, tile_lists.hpp)
     int cut_budget = W_CUT_BUDGET;  // RT_TILE_MASK_CUT=n (4 .. 65536): the largest cut the mask is computed from
     bool ocone = true;        // RT_OCONE=0: no origin cones (reflection queries always run case (b), ocone.hpp)
     int ocone_dim = 128;      // RT_OCONE_DIM=n: the origin-cone grid's cells along the scene's longest axis
@@ -254,6 +257,7 @@ public:
     int kernel_times(float* ms, int n);
     int band_counters(unsigned long long out[2]);
     int tile_mask(int src, uint32_t* out, int64_t cap, int32_t info[5]);   // rt_tile_mask
+    int tile_lists(int src, int32_t* out, int64_t cap, int32_t info[5]);   // rt_tile_lists
     int tile_starts(int src, uint32_t* out, int64_t cap, int32_t info[3]); // rt_tile_starts
     int debug_read(uint64_t* out, int64_t n);   // diagnostic builds: the per-wave records of the last frame
     int tile_costs(uint32_t* out, int64_t n, int32_t* tiles_x, int32_t* tiles_y);   // trace_frame's last tile costs
@@ -492,15 +496,47 @@ private:
         uint32_t launches = 0; // the stream's launches in a row with these words
         WMaskCam cam{};        // the camera the words were computed for
         uint64_t cut_gen = 0;  // and the cut (0: no words yet)
+        // the tile lists (tile_lists.hpp) of the stream's last launch with lists, behind the words
+        // in the same allocation (at list_off 4-byte words; KParams::list_off): rebuilt on the stream when the
+        // words were recomputed or the launch's layout (list_key, L: its band map on the device) changed
+        bool lists_valid = false;
+        uint64_t list_key = 0;
+        int32_t list_off = 0;
+        TileLayout L{};
+        // whether the stream's launches take the lists (the list kernel) or leave them (the plain kernel): decided
+        // once per resident tree from a launch's own figures, read back behind it without a wait (probe_lists):
+        // -1 not decided yet (the lists are taken), 1 taken, 0 left
+        int list_use = -1;
+        uint64_t use_gen = 0;        // the cut the decision (or its absence) belongs to
+        uint32_t list_launches = 0;  // launches given lists while undecided
+        bool probe_pending = false;
+        struct Probe {               // pinned: the launch's tile-cost sum and max, then the two list counts
+            unsigned long long* host = nullptr;
+            hipEvent_t ev = nullptr;
+            ~Probe()
+            {
+                if (host) hipHostFree(host);
+                if (ev) hipEventDestroy(ev);
+            }
+        } probe;
     };
+    // The lists pay where the tickets they remove are a visible share of the launch's work: a removed ticket is
+    // worth about LIST_TICKET_CYCLES wave-cycles (C4: ~3,300 in the masked tile's body, ~6,500 of dequeue, DESIGN.md
+    // 5.14); below LIST_MIN_SHARE of the launch's tile cycles the list queue costs more than it saves (hair1m:
+    // 0.6% estimated, 0.8% lost; C4: 15%, 4.8% won).
+    static constexpr unsigned long long LIST_TICKET_CYCLES = 10000;
+    static constexpr unsigned long long LIST_MIN_SHARE_INV = 50;   // 2%
+    int probe_lists(const KParams& P, hipStream_t stream);
+    MaskSlot* lists_slot_ = nullptr;   // the slot whose lists the launch in preparation was given
     DevBuf d_cut_;
     bool cut_valid_ = false, mask_seen_ = false;
     uint64_t cut_gen_ = 0;
     MaskSlot mask_main_;       // rt_ray_trace's (stream_)
     MaskSlot* mask_last_ = nullptr;
+    bool lists_last_ = false;  // the last launch was given tile lists (mask_last_'s)
     bool starts_last_ = false; // the last launch was given entry sets (mask_last_->starts)
     Fence cut_fence_;
-    int prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M);
+    int prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M, uint64_t layout_key = 0);
     DevBuf d_dbg_;                          // diagnostic per-wave records (RT_DEBUG_WAVES)
     bool ssao_ready_ = false;   // the buffers hold the last frame's z / normals
     // raster path: per-triangle piece counts / offsets, the piece table and its texcoords, the z-key

@@ -549,6 +549,19 @@ class Renderer:
         self._call("rt_tile_starts", int(src), ptr(sets, _u32p), sets.size, ptr(info, _i32p))
         return sets, bool(info[2])
 
+    def tile_lists(self, src=0):
+        """The last frame launch's tile lists (rt_tile_lists) -> (covered, clear, dict): the launch's 8 x 8 tiles
+        (row-major over its local rows) that the queue handed out and those filled with the background at the
+        waves' exit, each ascending.  src 0: the device's lists, 1: the host's recomputation from the mask
+        words.  dict: 'on' (False: the launch had no lists), 'tiles_x', 'tiles_y'."""
+        info = np.zeros(5, np.int32)
+        self._call("rt_tile_lists", int(src), None, 0, ptr(info, _i32p))
+        tiles = np.zeros(max(1, int(info[2]) + int(info[3])), np.int32)
+        self._call("rt_tile_lists", int(src), ptr(tiles, _i32p), tiles.size, ptr(info, _i32p))
+        nc, nk = int(info[2]), int(info[3])
+        return tiles[:nc].copy(), tiles[nc:nc + nk].copy(), {"on": bool(info[4]), "tiles_x": int(info[0]),
+                                                             "tiles_y": int(info[1])}
+
     # -- convenience ----------------------------------------------------------------
     def load_scene(self, sc: SceneData, st: RenderSettings):
         """Settings, camera, light, materials, geometry and textures of a SceneData."""

@@ -14,7 +14,9 @@ os.environ.setdefault("RT_ASYNC_ACCEL", "0")   # every frame on the wide BVH (DE
 from raytracercpp_amd import scenes
 from raytracercpp_amd.renderer import Renderer
 
-NAMES = ["tile setup", "ray generation", "primary query", "shading", "shadow query", "framebuffer", "dequeue"]
+# (a library from before the tile lists leaves the eighth word 0 and books its masked tiles under "dequeue")
+NAMES = ["tile setup", "ray generation", "primary query", "shading", "shadow query", "framebuffer", "dequeue",
+         "masked tiles, exit fill"]
 sc, st = scenes.sphere1m()
 if "--miss" in sys.argv:   # every primary ray misses (the sphere moved behind the camera)
     import dataclasses
@@ -24,12 +26,12 @@ r.load_scene(sc, st)
 for _ in range(3):
     r.ray_trace()
 s = r.stats()
-d = r.debug_read(16384 * 8).reshape(-1, 8)[:, :7].astype(np.float64)
+d = r.debug_read(16384 * 8).reshape(-1, 8)[:, :len(NAMES)].astype(np.float64)
 d = d[d.sum(1) > 0]
 tot = d.sum()
 print(f"kernel ms {s['kernel_ms']:.3f}  waves {len(d)}  mean cycles per wave {d.sum(1).mean():.0f}")
 for k, n in enumerate(NAMES):
-    print(f"  {n:16s} {d[:, k].sum() / tot * 100:6.1f} %   mean per wave {d[:, k].mean():10.0f} cycles")
+    print(f"  {n:24s} {d[:, k].sum() / tot * 100:6.1f} %   mean per wave {d[:, k].mean():10.0f} cycles")
 w = d.sum(1)
 q = np.quantile(w, [0.5, 0.9, 0.99, 1.0])
 print(f"  cycles per wave: median {q[0]:.0f}  p90 {q[1]:.0f}  p99 {q[2]:.0f}  max {q[3]:.0f}")

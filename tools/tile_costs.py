@@ -52,7 +52,8 @@ def gpu(name, frames, out):
         try:
             cov, info = r.tile_mask(0)
             print(f"  tile mask: on {info['on']}, cut {info['cut']} entries, {int((~cov).sum())} of {cov.size} tiles masked; "
-                  f"their cycles {c[:cov.shape[0], :cov.shape[1]][~cov].sum():.4g}")
+                  f"their cycles {c[:cov.shape[0], :cov.shape[1]][~cov].sum():.4g}"
+                  " (with tile lists, DESIGN.md 5.14: each one's share of its exit-fill step, not a dequeue and a tile body)")
         except Exception as e:   # (a library without rt_tile_mask)
             print(f"  tile mask: none ({e})")
     mean = v.mean()
