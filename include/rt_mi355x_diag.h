@@ -90,6 +90,10 @@ typedef struct rt_entry_probe {
     uint32_t *sets;                       /* optional, [block rows][blocks per row][4]: the entry sets */
     int64_t info[4];                      /* out: blocks per row, block rows, 1 when the camera has a mask, covered blocks */
     int64_t depth_hist[16];               /* out: the links other than the root, by their node's depth (15: deeper) */
+    int32_t no_cull;                      /* 1: without the block's back-face test (RT_ENTRY_CULL=0's sets) */
+    int32_t reserved;                     /* 0 */
+    int64_t close_hist[4];                /* out: the links of the covered blocks by what closed them: a covering leaf
+                                             child, more covering children than fan, the depth cap, the budget k */
 } rt_entry_probe;
 int rt_wbvh_query_ex(const float *tri9, int64_t n, int32_t max_depth, int32_t leaf_max_obj_count, const float *orig,
                      const float *dir, int64_t nrays, const float *cam, const float *light, int32_t shadow_rays,

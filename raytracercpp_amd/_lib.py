@@ -76,6 +76,7 @@ class RtEntryProbe(C.Structure):
         ("proj_inv", C.c_float * 16), ("cam_to_world", C.c_float * 16), ("rw", C.c_int32), ("rh", C.c_int32),
         ("k", C.c_int32), ("fan", C.c_int32), ("depth", C.c_int32), ("quick", C.c_int32),
         ("pixel", _i32p), ("sets", _u32p), ("info", C.c_int64 * 4), ("depth_hist", C.c_int64 * 16),
+        ("no_cull", C.c_int32), ("reserved", C.c_int32), ("close_hist", C.c_int64 * 4),
     ]
 
 
@@ -444,9 +445,9 @@ def wbvh_query(tri9, orig, dirs, max_depth=12, leaf=40, cam=None, light=None, sh
     1 certified hit, 2 not certified.  cam / light: the frame's grazing-risk points (rays from cam
     read the camera's bits); shadow_rays: orig / dirs are hit points and normals, traced as
     is_shadowed's rays towards light.  rays_out: (o, d) of the queried rays are appended.
-    entry: dict(proj_inv, cam_to_world, rw, rh, pixel [n, 2][, k, fan, depth, quick]) -- the camera rays start at
-    their blocks' entry sets; it receives 'sets' [block rows, blocks per row, 4], 'has_mask',
-    'covered' and 'depth_hist'."""
+    entry: dict(proj_inv, cam_to_world, rw, rh, pixel [n, 2][, k, fan, depth, quick, no_cull]) -- the camera rays
+    start at their blocks' entry sets; it receives 'sets' [block rows, blocks per row, 4],
+    'has_mask', 'covered', 'depth_hist' and 'close_hist'."""
     tri9 = f32(tri9).reshape(-1, 9)
     o = f32(orig).reshape(-1, 3)
     d = f32(dirs).reshape(-1, 3)
@@ -468,6 +469,7 @@ def wbvh_query(tri9, orig, dirs, max_depth=12, leaf=40, cam=None, light=None, sh
         ep.rw, ep.rh = int(entry["rw"]), int(entry["rh"])
         ep.k, ep.fan, ep.depth = (int(entry.get(x, 0)) for x in ("k", "fan", "depth"))
         ep.quick = int(entry.get("quick", 0))
+        ep.no_cull = int(entry.get("no_cull", 0))
         pix = np.ascontiguousarray(entry["pixel"], np.int32).reshape(-1, 2)
         assert pix.shape[0] == n
         sets = np.zeros(((ep.rh + 7) // 8, (ep.rw + 7) // 8, 4), np.uint32)
@@ -482,7 +484,8 @@ def wbvh_query(tri9, orig, dirs, max_depth=12, leaf=40, cam=None, light=None, sh
                                  None if oc_stats is None else ptr(oc_stats, _i64p),
                                  None if ep is None else C.byref(ep)), "rt_wbvh_query")
     if ep is not None:
-        entry.update(sets=sets, has_mask=bool(ep.info[2]), covered=int(ep.info[3]), depth_hist=[int(x) for x in ep.depth_hist])
+        entry.update(sets=sets, has_mask=bool(ep.info[2]), covered=int(ep.info[3]), depth_hist=[int(x) for x in ep.depth_hist],
+                     close_hist=[int(x) for x in ep.close_hist])
     keys = ("nodes", "leaves", "max_leaf", "depth", "node_visits", "tri_tests", "violations", "sah_x1000")
     out = (st, ids, t, u, v, dict(zip(keys, map(int, stats))), (float(ms[0]), float(ms[1])))
     return out + (oo, do) if rays_out else out

@@ -1340,7 +1340,7 @@ int rt_wbvh_query_ex(const float* tri9, int64_t n, int32_t max_depth, int32_t le
             }
         }
         // the blocks' entry sets (renderer.cpp prepare_mask: the cut, the mask, then the entry search)
-        std::vector<uint32_t> esets;
+        std::vector<uint32_t> esets, ewords;
         int ebw = 0;
         if (entry) {
             int mode;
@@ -1348,21 +1348,24 @@ int rt_wbvh_query_ex(const float* tri9, int64_t n, int32_t max_depth, int32_t le
             rt::wbvh_proj_shortcut(entry->proj_inv, mode, pw);
             const float* c = entry->cam_to_world;
             const int affine = c[12] == 0.0f && c[13] == 0.0f && c[14] == 0.0f && c[15] == 1.0f;
-            const rt::WMaskCam C = rt::wbvh_mask_cam(entry->proj_inv, c, mode, pw, affine, cam, light, S, W_QS_CLOSEST,
-                                                     entry->rw, entry->rh);
+            rt::WMaskCam C = rt::wbvh_mask_cam(entry->proj_inv, c, mode, pw, affine, cam, light, S, W_QS_CLOSEST, entry->rw,
+                                               entry->rh);
+            if (entry->no_cull)
+                C.cull = 0;
+            const int ek = entry->k > 0 ? entry->k : W_ENTRY_K, efan = entry->fan > 0 ? entry->fan : rt::wbvh_entry_fan(C),
+                      edepth = entry->depth > 0 ? entry->depth : W_CUT_DEPTH;
             entry->info[0] = C.bw;
             entry->info[1] = C.bh;
             entry->info[2] = usable && C.valid;
             entry->info[3] = 0;
             if (usable && C.valid) {
-                std::vector<uint32_t> cut, words;
+                std::vector<uint32_t> cut;
+                std::vector<uint32_t>& words = ewords;
                 rt::wbvh_cut_host(w.nodes.data(), (int64_t)w.nodes.size(), W_CUT_BUDGET, W_CUT_DEPTH, W_QS_CLOSEST, cut);
                 rt::wbvh_mask_host(w.nodes.data(), (int64_t)w.nodes.size(), w.parent.data(), cut, C, words);
                 for (uint32_t x : words)
                     entry->info[3] += __builtin_popcount(x);
-                rt::wbvh_entry_host(w.nodes.data(), (int64_t)w.nodes.size(), C, words.data(), entry->k > 0 ? entry->k : W_ENTRY_K,
-                                    entry->fan > 0 ? entry->fan : W_ENTRY_FAN, entry->depth > 0 ? entry->depth : W_CUT_DEPTH,
-                                    esets);
+                rt::wbvh_entry_host(w.nodes.data(), (int64_t)w.nodes.size(), C, words.data(), ek, efan, edepth, esets);
                 ebw = C.bw;
             }
             if (entry->sets) {
@@ -1381,6 +1384,24 @@ int rt_wbvh_query_ex(const float* tri9, int64_t n, int32_t max_depth, int32_t le
                         dep++;
                     entry->depth_hist[dep]++;
                 }
+            // what closed each link of the covered blocks, in the order of wbvh_entry_block's own test (a link that
+            // passes the first three was closed by the budget; an emptied frontier, stored as the root, is not counted)
+            for (int k = 0; k < 4; k++)
+                entry->close_hist[k] = 0;
+            for (size_t i = 0; i < esets.size(); i++) {
+                const uint32_t l = esets[i];
+                const int bx = (int)((i / rt::W_ENTRY_MAX) % (size_t)C.bw), by = (int)((i / rt::W_ENTRY_MAX) / (size_t)C.bw);
+                if (l == rt::W_EMPTY || !((ewords[(size_t)by * C.wpr + (bx >> 5)] >> (bx & 31)) & 1u))
+                    continue;
+                int dep = 0;
+                for (uint32_t x = l; dep < 64 && w.parent[x] != rt::W_EMPTY; x = w.parent[x] >> 2)
+                    dep++;
+                uint32_t ch[rt::W_WIDTH];
+                bool inner;
+                const int cnt = rt::wbvh_entry_cover(w.nodes[l], (int64_t)w.nodes.size(), C, bx, by, ch, inner);
+                if (cnt > 0)
+                    entry->close_hist[!inner ? 0 : cnt > efan ? 1 : dep + 1 >= edepth ? 2 : 3]++;
+            }
         }
         std::atomic<int64_t> work_n{0}, work_t{0}, n_nob{0};
         const bool probe_hi = std::getenv("RT_WQ_PROBE_HI") != nullptr;

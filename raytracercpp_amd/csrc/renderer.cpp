@@ -128,6 +128,7 @@ Knobs Knobs::from_env()
     k.scene_bound = flag("RT_SCENE_BOUND", k.scene_bound);
     k.tile_mask = flag("RT_TILE_MASK", k.tile_mask);
     k.tile_start = flag("RT_TILE_START", k.tile_start);
+    k.entry_cull = flag("RT_ENTRY_CULL", k.entry_cull);
     k.tile_list = flag("RT_TILE_LIST", k.tile_list);
     k.cut_budget = std::min((int)W_CUT_MAX, std::max((int)W_WIDTH, num("RT_TILE_MASK_CUT", k.cut_budget)));
     k.ocone = flag("RT_OCONE", k.ocone);
@@ -2487,10 +2488,11 @@ int Renderer::prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M, uint64_t
     if (!knobs_.tile_mask || !P.wnodes || !P.plain || P.has_reflection || P.zbuf || P.nbuf || wide_.nn <= 0 || !wide_.b_links.p ||
         s_.hybrid_rasterization_tracing)
         return RT_OK;
-    const WMaskCam C = wbvh_mask_cam(P.proj_inv, P.cam_to_world, P.proj_mode, P.proj_w, P.c2w_affine, P.cam_pos, P.light,
-                                     P.scene_scale, W_QS_CLOSEST, P.rw, P.rh);
+    WMaskCam C = wbvh_mask_cam(P.proj_inv, P.cam_to_world, P.proj_mode, P.proj_w, P.c2w_affine, P.cam_pos, P.light,
+                               P.scene_scale, W_QS_CLOSEST, P.rw, P.rh);
     if (!C.valid)
         return RT_OK;
+    C.cull = knobs_.entry_cull ? 1 : 0;
     hipError_t e;
     if (!cut_valid_) {
         if (wait_slots(stream) != RT_OK)
@@ -2533,7 +2535,7 @@ int Renderer::prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M, uint64_t
     if (knobs_.tile_start && !M.starts_valid && M.launches >= 2) {
         if ((e = M.starts.reserve((size_t)C.bh * C.bw * sizeof(uint4))) != hipSuccess)
             return hip_fail(e, "hipMalloc (entry sets)");
-        if ((e = rt_launch_wide_entry(P.wnodes, (int)wide_.nn, &C, M.words.as<uint32_t>(), W_ENTRY_K, W_ENTRY_FAN,
+        if ((e = rt_launch_wide_entry(P.wnodes, (int)wide_.nn, &C, M.words.as<uint32_t>(), W_ENTRY_K, wbvh_entry_fan(C),
                                       W_CUT_DEPTH, M.starts.as<uint4>(), stream)) != hipSuccess)
             return hip_fail(e, "wide_entry_kernel");
         M.starts_valid = true;
@@ -3150,7 +3152,7 @@ int Renderer::tile_starts(int src, uint32_t* out, int64_t cap, int32_t info[3])
         if ((e = hipMemcpy(nodes.data(), wide_.nodes(), nodes.size() * sizeof(WNode), hipMemcpyDeviceToHost)) != hipSuccess ||
             (e = hipMemcpy(words.data(), mask_last_->words.p, words.size() * 4, hipMemcpyDeviceToHost)) != hipSuccess)
             return hip_fail(e, "download (wide BVH nodes, mask words)");
-        wbvh_entry_host(nodes.data(), (int64_t)nodes.size(), C, words.data(), W_ENTRY_K, W_ENTRY_FAN, W_CUT_DEPTH, sets);
+        wbvh_entry_host(nodes.data(), (int64_t)nodes.size(), C, words.data(), W_ENTRY_K, wbvh_entry_fan(C), W_CUT_DEPTH, sets);
         std::memcpy(out, sets.data(), nw * 4);
     }
     return RT_OK;

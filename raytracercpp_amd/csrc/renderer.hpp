@@ -146,6 +146,8 @@ struct Knobs {
                               // the scene bound, wbvh.hpp wbvh_mask_rect)
     bool tile_start = true;   // RT_TILE_START=0: no entry sets (every camera ray starts its wide query at the root,
                               // wbvh.hpp wbvh_entry_block); no mask, no entry sets
+    bool entry_cull = true;   // RT_ENTRY_CULL=0: the entry search keeps the subtrees that face away from a whole block
+                              // (wbvh.hpp wbvh_entry_backfacing): the sets of the search without it
     bool tile_list = true;    // RT_TILE_LIST=0: no tile lists (the queue hands out every tile and the masked ones are
                               // filled there, tile_lists.hpp)
     int cut_budget = W_CUT_BUDGET;  // RT_TILE_MASK_CUT=n (4 .. 65536): the largest cut the mask is computed from

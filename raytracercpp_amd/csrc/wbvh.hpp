@@ -766,9 +766,11 @@ inline void wbvh_cut_host(const WNode* nodes, int64_t nnodes, int budget, int ma
 // inverse (double), so a point P has (a, b, s) = Minv (P - cam) and lies on the line of pixel (a / s, b /
 // s), for s of either sign (the bound's test is the line's).  guard (pixels) covers the float rounding
 // of camera_dir against the exact map and the mask's own rounding (wbvh_mask_cam).  scale (tests): each
-// cut box shrunk about its centre.
+// cut box shrunk about its centre.  cull: the entry search's back-face test (wbvh_entry_backfacing; 0: off,
+// 1: on, 2 (tests, unsound): the block's centre alone).
 struct WMaskCam {
     double Minv[9];
+    double M[9];
     double guard, scale;
     float cam[3];
     float S, QS;
@@ -776,6 +778,8 @@ struct WMaskCam {
     int32_t bw, bh, wpr;    // 8 x 8 blocks, 32-bit words per block row: block (bx, by) is bit bx & 31 of word by wpr + (bx >> 5)
     int32_t light_finite;
     int32_t valid;
+    int32_t cull;
+    int32_t pad;            // (no padding bytes: renderer.cpp prepare_mask compares cameras with memcmp)
 };
 
 // valid = 0 (no mask): a general projection or camera matrix, non-finite values, a singular M, or a camera
@@ -857,7 +861,10 @@ inline WMaskCam wbvh_mask_cam(const float proj_inv[16], const float c2w[16], int
     const double shift = 2.0 * (std::max(rn[0], rn[1]) * E + std::max(rw, rh) * ds);
     if (!(res < 1e-9) || !(ds <= 0.5) || !(shift <= 1.0))
         return C;
+    for (int i = 0; i < 9; i++)
+        C.M[i] = M[i];
     C.guard = guard_override ? *guard_override : 1.0 + 4.0 * shift;
+    C.cull = 1;
     C.valid = 1;
     return C;
 }
@@ -995,7 +1002,8 @@ inline void wbvh_mask_host(const WNode* nodes, int64_t nnodes, const uint32_t* p
 // ---------------------------------------------------------------------------------
 // Entry nodes: where the camera rays of an 8 x 8 block can go, found once per camera.  A
 // camera ray enters child j of node N only if its pixel lies in wbvh_mask_rect(N, j, C) (5.12), so the rays
-// of block b that reach N go on into c(N) = the non-empty children whose rectangle holds b, and nowhere else.
+// of block b that reach N go on into c(N) = the non-empty children whose rectangle holds b and that do not
+// face away from every ray of b (wbvh_entry_backfacing), and nowhere else.
 // Top-down from the root, a frontier node N is replaced by the child nodes of c(N) while every member of
 // c(N) is an inner node (no triangle is ever tested above the frontier), |c(N)| <= fan, the frontier stays
 // within K nodes and below max_depth; a node with an empty c(N) is dropped.  The block's primary queries
@@ -1008,8 +1016,17 @@ constexpr int W_ENTRY_MAX = 4;   // links per block (one uint4)
 #define W_ENTRY_K 4
 #endif
 #ifndef W_ENTRY_FAN
-#define W_ENTRY_FAN 3   // (tools/visit_probe.py, profiles/entry_nodes/host_probe.log: K 4, fan 3 saves the most)
+// (tools/visit_probe.py, profiles/entry_cull/host_probe_*.log: with the back-face test K 4, fan 4 saves the most on
+// sphere1m, hair1m and robot1080)
+#define W_ENTRY_FAN 4
 #endif
+// the fan of the search without the back-face test (RT_ENTRY_CULL=0: the sets as they were before it, for A/B runs;
+// profiles/entry_nodes/host_probe.log: fan 3 saved the most there)
+constexpr int W_ENTRY_FAN_UNCULLED = 3;
+inline int wbvh_entry_fan(const WMaskCam& C)   // the renderer's fan for camera C
+{
+    return C.cull ? W_ENTRY_FAN : W_ENTRY_FAN_UNCULLED;
+}
 
 struct WEntrySet {
     uint32_t link[W_ENTRY_MAX];
@@ -1032,6 +1049,62 @@ RT_HD double wbvh_entry_dist(const WNode& N, const float cam[3])
         s += g * g;
     }
     return s == s ? s : INFINITY;
+}
+
+// The block's back-face test (C.cull): child j of N is dropped from c(N) when every camera ray of block (bx, by)
+// skips it at N by wbvh_closest's cone test, a > c cstep in float (WNode: every triangle below j faces away
+// from such a ray).  A pixel's direction before normalisation is d = M (x, y, 1), and camera_dir's float
+// direction is a positive multiple of M (x', y', 1) with (x', y') within C.guard of the pixel (wbvh_mask_cam: the
+// third coordinate stays above 1/2).  f(d) = N_j . d - k |d| with k >= 0 is concave and positively homogeneous, so
+// over the rays of the rectangle [8 bx - guard, 8 bx + 7 + guard] x [8 by - guard, 8 by + 7 + guard] it is
+// smallest at one of the four corners: f > 0 there gives f > 0 for every float direction of the block.  The
+// margin in k = c W_CONE_STEP (1 + 2^-12) + 2^-10 makes that imply the ray's own float decision: its a is
+// a sum of three float products, within 3 u |N_j| |d| <= 3 2^-24 220 |d| < 4e-5 |d| of N_j . d; its threshold
+// c cstep is at most c W_CONE_STEP |d| (1 + 2^-20)(1 + 2^-22)(1 + u)^3 <= c W_CONE_STEP |d| (1 + 2^-18) (setup:
+// the square root and the dot within 2^-22, rounded up by 2^-20, two more products).  2^-10 is 25 times the
+// first, 2^-12 sixty-four times the second, and together they cost at most 0.056 of a code's step of 0.88.
+// Evaluated in double without a square root or a division (a > 0 and a^2 > k^2 |d|^2; double's rounding,
+// 1e-15 relative, is far inside the margin), so the host and the device decide alike.  Code 255: no cone.
+constexpr double W_CULL_REL = 0x1p-12, W_CULL_ABS = 0x1p-10;
+
+RT_HD bool wbvh_entry_backfacing(const WNode& N, int j, const WMaskCam& C, int bx, int by)
+{
+    const uint32_t nr = N.nrm[j];
+    if (C.cull == 0 || (nr >> 24) == 255u)
+        return false;
+    const double n[3] = {(double)(int8_t)(nr & 0xffu), (double)(int8_t)((nr >> 8) & 0xffu), (double)(int8_t)((nr >> 16) & 0xffu)};
+    const double k = (double)(nr >> 24) * (double)W_CONE_STEP * (1.0 + W_CULL_REL) + W_CULL_ABS;
+    const double x0 = 8.0 * bx - C.guard, x1 = 8.0 * bx + 7.0 + C.guard;
+    const double y0 = 8.0 * by - C.guard, y1 = 8.0 * by + 7.0 + C.guard;
+    const int corners = C.cull == 2 ? 1 : 4;
+    for (int q = 0; q < corners; q++) {
+        const double x = C.cull == 2 ? 0.5 * (x0 + x1) : ((q & 1) ? x1 : x0);
+        const double y = C.cull == 2 ? 0.5 * (y0 + y1) : ((q & 2) ? y1 : y0);
+        const double dx = C.M[0] * x + C.M[1] * y + C.M[2];
+        const double dy = C.M[3] * x + C.M[4] * y + C.M[5];
+        const double dz = C.M[6] * x + C.M[7] * y + C.M[8];
+        const double a = n[0] * dx + n[1] * dy + n[2] * dz;
+        if (!(a > 0.0 && a * a > k * k * (dx * dx + dy * dy + dz * dz)))
+            return false;
+    }
+    return true;
+}
+
+// c(N) for block (bx, by): the non-empty children of N that face some ray of the block (the four dot products
+// first: they are cheaper than the rectangle's sixteen divisions) and whose rectangle holds it.  inner: every
+// one of them is an inner node of the tree
+RT_HD int wbvh_entry_cover(const WNode& N, int64_t nnodes, const WMaskCam& C, int bx, int by, uint32_t ch[W_WIDTH], bool& inner)
+{
+    int cnt = 0;
+    inner = true;
+    for (int j = 0; j < W_WIDTH; j++) {
+        const uint32_t c = N.child[j];
+        if (c == W_EMPTY || wbvh_entry_backfacing(N, j, C, bx, by) || !wbvh_rect_holds(wbvh_mask_rect(N, j, C), bx, by))
+            continue;
+        inner = inner && !(c & W_LEAF) && (int64_t)c < nnodes;
+        ch[cnt++] = c;
+    }
+    return cnt;
 }
 
 RT_HD WEntrySet wbvh_entry_block(const WNode* nodes, int64_t nnodes, const WMaskCam& C, int bx, int by, int K, int fan,
@@ -1061,15 +1134,8 @@ RT_HD WEntrySet wbvh_entry_block(const WNode* nodes, int64_t nnodes, const WMask
             break;
         const WNode& N = nodes[fn[i]];
         uint32_t ch[W_WIDTH];
-        int cnt = 0;
-        bool inner = true;
-        for (int j = 0; j < W_WIDTH; j++) {
-            const uint32_t c = N.child[j];
-            if (c == W_EMPTY || !wbvh_rect_holds(wbvh_mask_rect(N, j, C), bx, by))
-                continue;
-            inner = inner && !(c & W_LEAF) && (int64_t)c < nnodes;
-            ch[cnt++] = c;
-        }
+        bool inner;
+        const int cnt = wbvh_entry_cover(N, nnodes, C, bx, by, ch, inner);
         if (cnt == 0) {   // no ray of the block goes below N
             for (int k = i + 1; k < n; k++) {
                 fn[k - 1] = fn[k];

@@ -5,8 +5,9 @@ build ...) the same rays price a variant of the child test.
     python tools/visit_probe.py [config] [tile_row_stride]
 Rays: every tile_row_stride-th row of 8x8 tiles (all 8 rows of each), so tile maxima are exact.
 Then (RT_PROBE_ENTRY=0: not) the same primary rays started at their blocks' entry sets, per
-policy: visits per hit and per miss ray, the sets' sizes and depths, and the queries whose status differs from
-the root query's (profiles/entry_nodes/host_probe.log)."""
+policy, without and with the search's back-face test (cull 0 / 1): visits per hit and per miss ray, the sets' sizes
+and depths, what closed the links (a covering leaf child / more covering children than fan / the depth cap / the
+budget K), and the queries whose status differs from the root query's (profiles/entry_cull/host_probe_*.log)."""
 import os
 import sys
 
@@ -70,11 +71,11 @@ def entry_table(name, sc, st, o, d, rows, rw, rh, st_root, n_root):
     blk = (pix[:, 1] >> 3) * ((rw + 7) // 8) + (pix[:, 0] >> 3)
     print(f"  entry sets ({name}, {len(o)} rays; from the root: {n_root[hit].mean():.3f} visits per hit ray, "
           f"{n_root[~hit].mean():.3f} per miss ray)")
-    print("  K fan | hit ray  miss ray  all rays | saved/hit | status differs | covered blocks: links 1/2/3/4, at the root | "
-          "link depth 1..12")
-    for k, fan in ((1, 1), (2, 2), (4, 1), (4, 2), (4, 3), (4, 4)):
+    print("  K fan cull | hit ray  miss ray  all rays | saved/hit | status differs | covered blocks: links 1/2/3/4, at the "
+          "root | closed by leaf/fan/depth/K | link depth 1..12")
+    for k, fan, cull in [(k, fan, c) for k, fan in ((1, 1), (2, 2), (4, 1), (4, 2), (4, 3), (4, 4)) for c in (0, 1)]:
         nodes = np.zeros(len(o), np.int32)
-        e = dict(proj_inv=sc.proj_inv, cam_to_world=sc.cam_to_world, rw=rw, rh=rh, pixel=pix, k=k, fan=fan)
+        e = dict(proj_inv=sc.proj_inv, cam_to_world=sc.cam_to_world, rw=rw, rh=rh, pixel=pix, k=k, fan=fan, no_cull=1 - cull)
         s2 = _lib.wbvh_query(sc.tri, o, d, st.bvh_max_depth, st.bvh_leaf_object_count, cam=sc.cam_pos, ray_nodes=nodes,
                              entry=e)[0]
         assert e["has_mask"], "the camera has no mask"
@@ -86,9 +87,11 @@ def entry_table(name, sc, st, o, d, rows, rw, rh, st_root, n_root):
         root = (ps[:, 0] == 0)
         cov = ~root | np.isin(probed, np.unique(blk[hit]))
         sizes = [int(((nl == i) & ~root & cov).sum()) for i in (1, 2, 3, 4)]
-        print(f"  {k} {fan}   | {nodes[hit].mean():7.3f}  {nodes[~hit].mean():7.3f}  {nodes.mean():7.3f}  | "
+        ch = e["close_hist"]
+        print(f"  {k} {fan}   {cull}    | {nodes[hit].mean():7.3f}  {nodes[~hit].mean():7.3f}  {nodes.mean():7.3f}  | "
               f"{n_root[hit].mean() - nodes[hit].mean():6.3f}    | {int((s2 != st_root).sum()):6d}         | "
-              f"{sizes[0]}/{sizes[1]}/{sizes[2]}/{sizes[3]}, {int((root & cov).sum())} | {e['depth_hist'][1:13]}")
+              f"{sizes[0]}/{sizes[1]}/{sizes[2]}/{sizes[3]}, {int((root & cov).sum())} | {ch[0]}/{ch[1]}/{ch[2]}/{ch[3]} | "
+              f"{e['depth_hist'][1:13]}")
 
 
 if __name__ == "__main__":
