@@ -467,6 +467,42 @@ int rt_is_shadowed_device(rt_renderer *r, const float *d_point, const float *d_n
                           uint8_t *d_shadowed, void *hip_stream);
 int rt_get_device_ray_queries(rt_renderer *r, int64_t calls[2], int64_t rays[2]);
 
+/* The shaded query on device memory (no reference counterpart).
+ * rt_trace_ray_device is rt_trace_ray (below) with every array in memory of the handle's device: d_orig / d_dir
+ * [n][3] floats in; d_rgba [n][4] floats out (required, 16-byte aligned: else RT_EINVAL); d_hit_src / d_t /
+ * d_found / d_shadowed [n] out, each of which may be NULL and is then not written.  Per ray it writes exactly
+ * what rt_trace_ray writes for that ray in the same renderer state, in every mode (quick or SAH wide BVH, before
+ * one is resident, exact mode, RT_WBVH=0, enable_bvh 0, every shading method, analytic shapes, textures, sky,
+ * reflections, rough reflections), with one exception: a scene the frames render with their plain pixel (no
+ * texture map, sky, analytic shape, debug shading or reflective material, over a resident wide BVH) takes that
+ * pixel's code, and its colour is the float RGBA a frame writes for the same ray (hit_src, t and the flags are
+ * rt_trace_ray's bit for bit); RT_SHADE_PLAIN=0, read by rt_create, sends such scenes through the generic code.
+ * first_ray: ray i draws the rough-reflection stream of pixel first_ray + i of a frame, so a batch split over
+ * several calls gives the bytes of one call; first_ray 0 is rt_trace_ray's keying.  RT_EINVAL for first_ray < 0
+ * or first_ray + n > 2^32.
+ * current_recursion_depth as in rt_trace_ray; negative: RT_EINVAL.  Past max_recursion_depth every ray gets what
+ * trace_ray returns there -- (0, 0, 0, 1), -1, -1.0f, 0, 0 -- from a fill kernel on hip_stream, and d_counts is
+ * left as it is.
+ * d_counts (int64 [2] in device memory, or NULL; the caller zeroes it): the kernel adds the call's shadow rays to
+ * [0] and its reflection rays to [1], the numbers rt_get_stats reports after rt_trace_ray on the same rays.
+ * rt_get_stats itself is not touched by this call, and the call shares nothing with band launches in flight.
+ * The stream contract, the pointer check and the refusals are rt_trace_rays_device's: the kernel runs on
+ * hip_stream in its order, only the caller's memory is written, the host does not wait and nothing is
+ * allocated; whatever later replaces what the kernel reads (geometry, materials, textures, the skybox, the wide
+ * BVH, the risk words) and rt_destroy first wait for it.  RT_EINVAL for a null d_orig / d_dir / d_rgba with
+ * n > 0, n < 0 or n > 2^30; n == 0: RT_OK, no launch.  Outputs must not overlap the inputs or each other (not
+ * checked).  The scene is validated as rt_trace_ray validates it, with the same codes (an enabled texture map
+ * that is missing: RT_EINVAL; reflective materials with max_recursion_depth > 15: RT_EUNSUPPORTED).
+ * rt_get_device_shaded_queries: calls[0..2] = launches of the shading kernel's three instances since rt_create
+ * ([0] plain, [1] generic, [2] reflective), rays[0..2] = the rays given to them; the fill past the depth limit
+ * counts in none. */
+int rt_trace_ray_device(rt_renderer *r, const float *d_orig, const float *d_dir, int64_t n,
+                        int32_t current_recursion_depth, int64_t first_ray,
+                        float *d_rgba, int32_t *d_hit_src, float *d_t,
+                        uint8_t *d_found, uint8_t *d_shadowed,
+                        int64_t *d_counts, void *hip_stream);
+int rt_get_device_shaded_queries(rt_renderer *r, int64_t calls[3], int64_t rays[3]);
+
 /* Renderer::trace_ray(ray, hit_info, current_recursion_depth, intersection_found)
  * (renderer.h:144, renderer.cpp:1008-1066) for n arbitrary rays (origins / directions [n][3]),
  * each with a fresh HitInfo: rgba [n][4] = the Color trace_ray returns (shading, shadow ray,

@@ -144,6 +144,9 @@ SIGNATURES = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_is_shadowed_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, _f32p, C.c_void_p, C.c_void_p]),
     "rt_get_device_ray_queries": (C.c_int, [_H, _i64p, _i64p]),
+    "rt_trace_ray_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_get_device_shaded_queries": (C.c_int, [_H, _i64p, _i64p]),
     "rt_trace_ray": (C.c_int, [_H, _f32p, _f32p, C.c_int64, C.c_int32, _f32p, _i32p, _f32p, _u8p, _u8p]),
     "rt_wide_query": (C.c_int, [_H, _f32p, _f32p, C.c_int64, C.c_int32, _f32p, _f32p, _i32p, _i32p, _f32p, _f32p, _f32p,
                                 _u8p]),
@@ -192,6 +195,8 @@ GEOMETRY_INPUT = ("rt_set_triangles_device", "rt_update_vertices_device", "rt_ge
                   "rt_gather_triangles_device", "rt_set_accel_deferred", "rt_get_accel_builds")
 # the device ray queries, likewise (tools/ray_query_time.py skips their rows for such a library)
 RAY_QUERIES = ("rt_trace_rays_device", "rt_is_shadowed_device", "rt_get_device_ray_queries")
+# the shaded device query, likewise
+SHADED_QUERIES = ("rt_trace_ray_device", "rt_get_device_shaded_queries")
 # the tile lists' read-back, likewise (an A/B run against the parent commit's library)
 TILE_LISTS = ("rt_tile_lists",)
 
@@ -218,7 +223,7 @@ def lib():
             pass
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            if name in GEOMETRY_INPUT + RAY_QUERIES + TILE_LISTS and os.environ.get("RT_LIB_PATH") and not hasattr(L, name):
+            if name in GEOMETRY_INPUT + RAY_QUERIES + SHADED_QUERIES + TILE_LISTS and os.environ.get("RT_LIB_PATH") and not hasattr(L, name):
                 continue
             fn = getattr(L, name)
             fn.restype = res
@@ -400,20 +405,53 @@ def _device_place(t, name, device):
         raise ValueError(f"{name}: the tensor is on GPU {t.device.index}, the renderer on GPU {int(device)}")
 
 
-def device_ray_out(t, name, dtype, n, device):
-    """An output tensor of a device ray query: ``dtype``, one dimension, at least n elements, placed as the
-    inputs; its pointer."""
+def device_ray_out(t, name, dtype, n, device, cols=None):
+    """An output tensor of a device ray query: ``dtype``, one dimension and at least n elements (cols: two
+    dimensions, at least n rows of ``cols``), contiguous, placed as the inputs; its pointer."""
+    _ray_out_form(t, name, dtype, n, cols)
+    _device_place(t, name, device)
+    return t.data_ptr()
+
+
+def _ray_out_form(t, name, dtype, n, cols):
     import torch
 
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name}: a torch tensor on the GPU is needed, not {type(t).__name__}")
     if t.dtype != dtype:
         raise TypeError(f"{name}: dtype {t.dtype}, {dtype} is needed")
-    if t.dim() != 1 or t.shape[0] < n:
+    if cols is not None:
+        if t.dim() != 2 or t.shape[1] != cols or t.shape[0] < n:
+            raise ValueError(f"{name}: shape {tuple(t.shape)}, [>= {n}, {cols}] is needed")
+    elif t.dim() != 1 or t.shape[0] < n:
         raise ValueError(f"{name}: shape {tuple(t.shape)}, [>= {n}] is needed")
     _contiguous(t, name)
-    _device_place(t, name, device)
-    return t.data_ptr()
+
+
+# the outputs of Renderer.trace_ray_device in the C call's order: (key, dtype, columns; None: [n])
+SHADE_OUT = (("rgba", "float32", 4), ("hit_src", "int32", None), ("t", "float32", None),
+             ("intersection_found", "uint8", None), ("shadowed", "uint8", None))
+
+
+def device_shade_outs(out, n, device):
+    """The checks of Renderer.trace_ray_device on its ``out`` dict: any subset of SHADE_OUT's keys that holds
+    rgba, each tensor checked as device_ray_out checks it (rgba: [>= n, 4]), what every tensor is before where any
+    lies; the five pointers, None for a key left out."""
+    import torch
+
+    if not isinstance(out, dict):
+        raise TypeError(f"out: a dict of torch tensors is needed, not {type(out).__name__}")
+    unknown = sorted(set(out) - {k for k, _, _ in SHADE_OUT})
+    if unknown:
+        raise ValueError(f"out: unknown key {unknown[0]!r}")
+    if "rgba" not in out:
+        raise ValueError("out: rgba is needed (the other outputs may be left out)")
+    given = [(k, dt, c) for k, dt, c in SHADE_OUT if k in out]
+    for k, dt, c in given:
+        _ray_out_form(out[k], k, getattr(torch, dt), n, c)
+    for k, _, _ in given:
+        _device_place(out[k], k, device)
+    return [out[k].data_ptr() if k in out else None for k, _, _ in SHADE_OUT]
 
 
 def load_obj(path, xform, mat_offset=0):

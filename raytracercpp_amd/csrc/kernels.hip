@@ -3743,6 +3743,78 @@ __global__ __launch_bounds__(BLOCK, RT_OCC) void trace_colors_kernel(KParams P_a
     if (nrefl) atomicAdd(&P.counters[1], (unsigned long long)nrefl);
 }
 
+// wave_count_add over 64 bits: the lanes' counts are 32-bit (trace_pixel's), and 64 of them need not fit 32 bits
+// together (a lane makes up to 16 + 16^2 + ... + 16^d reflection rays at 16 samples and depth d: 1.1 M at depth
+// 5, 72 M a wave, but 2^28 a lane from depth 7).  Every lane of the wave calls it.
+__device__ __forceinline__ void wave_count_add64(unsigned long long* ctr, unsigned long long v)
+{
+    for (int off = 32; off > 0; off >>= 1)
+        v += __shfl_xor(v, off);
+    if (__lane_id() == 0 && v)
+        atomicAdd(ctr, v);
+}
+
+// Renderer::trace_ray for a batch of rays that lie in the caller's device memory (rt_trace_ray_device): per ray
+// what trace_colors_kernel writes, one lane per ray.  Ray i draws the rough-reflection stream of pixel
+// first_ray + i.  Every output but the colour may be null; counts (optional): [0] += the call's shadow rays,
+// [1] += its reflection rays, one atomic per wave and word, so no lane leaves before the wave's sums.  It reads
+// nothing the frames write: no P.counters, no buffer of the handle's.
+// INST: SHADE_PLAIN -- the frames' plain pixel (trace_pixel<false, true>: the colour through shade_lit /
+// shade_shadow_emit / shade_finish, the pixel's values in LDS across the shadow query) at the plain kernel's
+// occupancy, for a scene with P.plain over a resident wide BVH; its rays start at the root (no entry set: they
+// are not a block's camera rays).  SHADE_GENERIC / SHADE_REFL: trace_colors_kernel's own two instances of
+// trace_pixel, the same expressions and so the same bytes.
+template <int INST>
+__global__ __launch_bounds__(BLOCK, INST == SHADE_PLAIN ? RT_OCC_PLAIN : RT_OCC) void shade_rays_kernel(
+    KParams P_arg, const float* __restrict__ orig, const float* __restrict__ dir, int n, uint32_t first_ray,
+    float4* __restrict__ out_rgba, int32_t* __restrict__ out_src, float* __restrict__ out_t,
+    uint8_t* __restrict__ out_found, uint8_t* __restrict__ out_shadow, unsigned long long* __restrict__ counts)
+{
+    const KParams& P = kernel_params();
+    (void)P_arg;
+    uint2* lv = lane_stack();
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    unsigned nshadow = 0, nrefl = 0;
+    if (i < n) {
+        const size_t j = 3 * (size_t)i;   // (in 64 bits, as closest_rays_kernel)
+        const v3 o = mk(orig[j], orig[j + 1], orig[j + 2]);
+        const v3 d = mk(dir[j], dir[j + 1], dir[j + 2]);
+        // (first_ray + n <= 2^32, checked on the host)
+        const uint32_t key = INST == SHADE_REFL ? pixel_seed(first_ray + (uint32_t)i, P.rng_seed) : 0u;
+        PixelOut po;
+        if (INST == SHADE_PLAIN)
+            po = trace_pixel<false, true>(P, o, d, lv, key, nshadow, nrefl, -1);
+        else
+            po = trace_pixel<INST == SHADE_REFL>(P, o, d, lv, key, nshadow, nrefl);
+        out_rgba[i] = make_float4(po.color.r, po.color.g, po.color.b, po.alpha);
+        if (out_src) out_src[i] = po.found ? po.src : -1;
+        if (out_t) out_t[i] = po.fin.t;
+        if (out_found) out_found[i] = po.found ? 1 : 0;
+        if (out_shadow) out_shadow[i] = (uint8_t)(po.found && po.shadowed);
+    }
+    if (counts) {
+        wave_count_add64(&counts[0], (unsigned long long)nshadow);
+        wave_count_add64(&counts[1], (unsigned long long)nrefl);
+    }
+}
+
+// rt_trace_ray_device past max_recursion_depth (renderer.cpp:1012-1013): Color(0.0f), the record untouched,
+// intersection_found false, for every ray
+__global__ __launch_bounds__(256) void shade_rays_fill_kernel(int n, float4* __restrict__ out_rgba,
+                                                              int32_t* __restrict__ out_src, float* __restrict__ out_t,
+                                                              uint8_t* __restrict__ out_found,
+                                                              uint8_t* __restrict__ out_shadow)
+{
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= n)
+        return;
+    out_rgba[i] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+    if (out_src) out_src[i] = -1;
+    if (out_t) out_t[i] = -1.0f;
+    if (out_found) out_found[i] = 0;
+    if (out_shadow) out_shadow[i] = 0;
+}
+
 // The wide BVH's triangle records and their metadata, gathered on the device from the octree's
 // (already uploaded) instead of uploading 64 B per triangle again: wide-BVH triangle k is octree
 // slot s = slot[k]; wmeta[k] = {s, its octree leaf, its caller index, that triangle's material}.
@@ -3927,6 +3999,35 @@ hipError_t rt_launch_trace_colors(const rt::KParams* P, bool refl, const float* 
     else
         hipLaunchKernelGGL(rt::trace_colors_kernel<false>, grid, block, lds, stream, *P, o, d, n, rgba, src, t, found,
                            shadow);
+    return hipGetLastError();
+}
+
+hipError_t rt_launch_shade_rays(const rt::KParams* P, int inst, const float* o, const float* d, int n,
+                                uint32_t first_ray, float4* rgba, int32_t* src, float* t, uint8_t* found,
+                                uint8_t* shadow, int64_t* counts, hipStream_t stream)
+{
+    if (n <= 0)
+        return hipSuccess;
+    // (the plain instance's lanes take the plain pixel's LDS entries, lds_bytes)
+    size_t lds = rt::lds_bytes(*P, inst == rt::SHADE_PLAIN);
+    dim3 grid((n + rt::BLOCK - 1) / rt::BLOCK), block(rt::BLOCK);
+    unsigned long long* c = reinterpret_cast<unsigned long long*>(counts);
+#define RT_SR(k) hipLaunchKernelGGL(rt::shade_rays_kernel<k>, grid, block, lds, stream, *P, o, d, n, first_ray, rgba, src, t, \
+                                    found, shadow, c)
+    if (inst == rt::SHADE_PLAIN) RT_SR(rt::SHADE_PLAIN);
+    else if (inst == rt::SHADE_REFL) RT_SR(rt::SHADE_REFL);
+    else RT_SR(rt::SHADE_GENERIC);
+#undef RT_SR
+    return hipGetLastError();
+}
+
+hipError_t rt_launch_shade_rays_fill(int n, float4* rgba, int32_t* src, float* t, uint8_t* found, uint8_t* shadow,
+                                     hipStream_t stream)
+{
+    if (n <= 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(rt::shade_rays_fill_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, rgba, src, t, found,
+                       shadow);
     return hipGetLastError();
 }
 

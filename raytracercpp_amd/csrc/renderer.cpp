@@ -103,6 +103,7 @@ Knobs Knobs::from_env()
     k.lslab = on("RT_LSLAB", true);
     k.plain = on("RT_PLAIN", true);
     k.plain_octree = on("RT_PLAIN_OCTREE", true);
+    k.shade_plain = on("RT_SHADE_PLAIN", true);
     k.quick_wbvh = on("RT_WBVH_QUICK_FIRST", true);
     k.fused_ssaa = on("RT_FUSED_SSAA", true);
     k.refl_engine = on("RT_REFL_ENGINE", true);
@@ -2757,11 +2758,14 @@ int Renderer::trace_rays(const float* orig, const float* dir, int64_t n, int32_t
     return RT_OK;
 }
 
-// Before a device ray query's launch (rt_trace_rays_device, rt_is_shadowed_device).  Nothing
-// of the scene is validated beyond what a frame's ensure_device_scene refuses: like trace_rays, the queries
-// read the triangles and the analytic shapes only, no material and no texture.
+// Before a device ray query's launch (rt_trace_rays_device, rt_is_shadowed_device, rt_trace_ray_device;
+// DESIGN.md 13).  For the first two nothing of the scene is validated beyond what a frame's
+// ensure_device_scene refuses: like trace_rays, they read the triangles and the analytic shapes only, no
+// material and no texture.  shaded: the query reads both, and the scene is validated as trace_ray_colors
+// validates it, with its codes.  reads_scene false (the shaded query past its depth limit): the launch reads
+// nothing of the scene, so P and the risk words are left alone.
 int Renderer::begin_ray_query(const char* what, const void* const* ptrs, int nptrs, int n_required, int64_t n,
-                              hipStream_t stream, KParams& P)
+                              hipStream_t stream, KParams& P, bool shaded, bool reads_scene)
 {
     bool null_arg = false;
     for (int i = 0; i < n_required; i++)
@@ -2774,8 +2778,14 @@ int Renderer::begin_ray_query(const char* what, const void* const* ptrs, int npt
     int rc = n > 0 ? check_device_pointers(ptrs, nptrs, device_, what, err_) : RT_OK;
     if (rc != RT_OK)
         return rc;
+    if (shaded) {
+        if (validate() != RT_OK)
+            return fail(RT_EINVAL, "invalid scene: material index out of range or enabled texture map missing");
+        if (check_frame() != RT_OK)
+            return fail(RT_EUNSUPPORTED, "reflective materials with max_recursion_depth > 15");
+    }
     rc = ensure_device_scene();
-    if (rc != RT_OK || n == 0)
+    if (rc != RT_OK || n == 0 || !reads_scene)
         return rc;
     fill_params(P);
     // (the stream waits for the risk words' computation, or computes them after the launches that read the
@@ -2783,6 +2793,7 @@ int Renderer::begin_ray_query(const char* what, const void* const* ptrs, int npt
     return prepare_risk(P, stream);
 }
 
+// kind: 0 closest hit, 1 shadow, 2 + rt::SHADE_* the shaded query's instance
 int Renderer::end_ray_query(int kind, int64_t n, hipStream_t stream)
 {
     hipError_t e = query_fence_.record(stream, fence_stream_);
@@ -2826,6 +2837,52 @@ void Renderer::device_ray_queries(int64_t calls[2], int64_t rays[2]) const
     for (int k = 0; k < 2; k++) {
         calls[k] = query_calls_[k];
         rays[k] = query_rays_[k];
+    }
+}
+
+// Renderer::trace_ray over n rays in memory of device_, on the caller's stream (rt_trace_ray_device, DESIGN.md
+// 13; kernels.hip shade_rays_kernel): trace_ray_colors' results per ray with no upload, download, allocation
+// or host wait, and nothing shared with band launches (the counts go to the caller's d_counts, not to
+// d_counters_)
+int Renderer::trace_ray_device(const float* d_orig, const float* d_dir, int64_t n, int depth, int64_t first_ray,
+                               float* d_rgba, int32_t* d_src, float* d_t, uint8_t* d_found, uint8_t* d_shadow,
+                               int64_t* d_counts, hipStream_t stream)
+{
+    // (ray i is keyed as pixel first_ray + i, a 32-bit pixel index; n is bounded first, so no sum overflows)
+    if (depth < 0 || n < 0 || n > (1 << 30) || first_ray < 0 || first_ray > (1ll << 32) - n)
+        return fail(RT_EINVAL, "trace_ray_device: bad arguments");
+    if (reinterpret_cast<uintptr_t>(d_rgba) & 15u)
+        return fail(RT_EINVAL, "trace_ray_device: d_rgba is not 16-byte aligned");
+    const void* const ptrs[] = {d_orig, d_dir, d_rgba, d_src, d_t, d_found, d_shadow, d_counts};
+    KParams P;
+    const bool past = depth > s_.max_recursion_depth;
+    int rc = begin_ray_query("trace_ray_device", ptrs, 8, 3, n, stream, P, true, !past);
+    if (rc != RT_OK || n == 0)
+        return rc;
+    hipError_t e;
+    if (past) {
+        // renderer.cpp:1012-1013: Color(0.0f), the record untouched, intersection_found false; no ray is traced
+        // and nothing of the scene is read (no parameters, no risk words), so neither the counts nor the fence move
+        e = rt_launch_shade_rays_fill((int)n, reinterpret_cast<float4*>(d_rgba), d_src, d_t, d_found, d_shadow, stream);
+        return e != hipSuccess ? hip_fail(e, "shade_rays_fill_kernel launch") : RT_OK;
+    }
+    P.max_recursion_depth = s_.max_recursion_depth - depth;   // only the difference is read
+    P.counters = nullptr;   // (the handle's counter words belong to the frames)
+    const int inst = P.has_reflection                           ? SHADE_REFL
+                     : P.plain && P.wnodes && knobs_.shade_plain ? SHADE_PLAIN
+                                                                 : SHADE_GENERIC;
+    e = rt_launch_shade_rays(&P, inst, d_orig, d_dir, (int)n, (uint32_t)first_ray, reinterpret_cast<float4*>(d_rgba),
+                             d_src, d_t, d_found, d_shadow, d_counts, stream);
+    if (e != hipSuccess)
+        return hip_fail(e, "shade_rays_kernel launch");
+    return end_ray_query(2 + inst, n, stream);
+}
+
+void Renderer::device_shaded_queries(int64_t calls[3], int64_t rays[3]) const
+{
+    for (int k = 0; k < 3; k++) {
+        calls[k] = query_calls_[2 + k];
+        rays[k] = query_rays_[2 + k];
     }
 }
 

@@ -112,6 +112,8 @@ struct Knobs {
                               // before the SAH tree is resident walk the octree; 5.9)
     bool plain_octree = true; // RT_PLAIN_OCTREE=0: frames on the octree path (before the wide BVH is resident,
                               // exact mode) take the general kernel, not the plain one (5.8)
+    bool shade_plain = true;  // RT_SHADE_PLAIN=0: rt_trace_ray_device sends plain scenes through its generic instance,
+                              // not the frames' plain pixel (kernels.hip shade_rays_kernel)
     bool fused_ssaa = true;   // RT_FUSED_SSAA=0: band launches downscale in a separate pass (7)
     bool refl_engine = true;  // RT_REFL_ENGINE=0: the one-lane-per-pixel recursive kernel (9)
     int refl_chunk_log2 = 27; // RT_REFL_CHUNK_LOG2 (10..27): sample slots per engine chunk
@@ -284,6 +286,13 @@ public:
                            uint8_t* d_shadowed, hipStream_t stream);
     // launches of the two kernels since rt_create and the rays given to them (rt_get_device_ray_queries)
     void device_ray_queries(int64_t calls[2], int64_t rays[2]) const;
+    // Renderer::trace_ray (shaded) over n rays in memory of device_ at current_recursion_depth 'depth', ray i keyed
+    // as pixel first_ray + i, on the caller's stream (rt_trace_ray_device); every output but d_rgba may be null
+    int trace_ray_device(const float* d_orig, const float* d_dir, int64_t n, int depth, int64_t first_ray, float* d_rgba,
+                         int32_t* d_src, float* d_t, uint8_t* d_found, uint8_t* d_shadow, int64_t* d_counts,
+                         hipStream_t stream);
+    // its launches and rays since rt_create by instance: plain, generic, reflective (rt_get_device_shaded_queries)
+    void device_shaded_queries(int64_t calls[3], int64_t rays[3]) const;
     // the frames' wide-BVH query and its status over n host rays (rt_wide_query)
     int wide_query(const float* orig, const float* dir, int64_t n, int kind, float* o_out, float* d_out,
                    int32_t* status, int32_t* id, float* t, float* u, float* v, uint8_t* shadow);
@@ -331,15 +340,17 @@ private:
     // (before buffers that launches read are replaced)
     int wait_slots(hipStream_t stream);
     int sync_slots();
-    // The device ray queries (trace_rays_device, is_shadowed_device).  query_fence_ follows the last launch
-    // on any stream: fence_stream_ runs in order, so the last record() comes after every earlier one.
+    // The device ray queries (trace_rays_device, is_shadowed_device, trace_ray_device).  query_fence_ follows the
+    // last launch on any stream: fence_stream_ runs in order, so the last record() comes after every earlier one.
     Fence query_fence_;
-    int64_t query_calls_[2] = {}, query_rays_[2] = {};   // closest hit, shadow
+    int64_t query_calls_[5] = {}, query_rays_[5] = {};   // closest hit, shadow, shaded: plain, generic, reflective
     // before a query launch on 'stream': the count and the pointers (n_required of them must not be null when
-    // n > 0; each must be memory of device_), the scene as a frame brings it up to date, P with its risk words
+    // n > 0; each must be memory of device_), the scene as a frame brings it up to date (shaded: validated as
+    // trace_ray_colors validates it first), P with its risk words (reads_scene false: neither; the launch reads
+    // nothing of the scene)
     int begin_ray_query(const char* what, const void* const* ptrs, int nptrs, int n_required, int64_t n,
-                        hipStream_t stream, KParams& P);
-    // after it: the fence and the counters (kind 0 closest hit, 1 shadow)
+                        hipStream_t stream, KParams& P, bool shaded = false, bool reads_scene = true);
+    // after it: the fence and the counters (kind 0 closest hit, 1 shadow, 2 + the shaded query's instance)
     int end_ray_query(int kind, int64_t n, hipStream_t stream);
 
     Knobs knobs_;

@@ -473,6 +473,40 @@ class Renderer:
         self._call("rt_get_device_ray_queries", ptr(calls, i64p), ptr(rays, i64p))
         return (int(calls[0]), int(calls[1])), (int(rays[0]), int(rays[1]))
 
+    def trace_ray_device(self, orig, dirs, current_recursion_depth=0, first_ray=0, out=None, counts=None, stream=None):
+        """rt_trace_ray_device: trace_ray (shaded) for rays in GPU memory, in the order of ``stream`` (a torch
+        stream; default the current one) and without a host wait -> dict(rgba float32 [n, 4], hit_src int32,
+        t float32, intersection_found uint8, shadowed uint8) of torch tensors, trace_ray's answers.  orig, dirs:
+        contiguous float32 [n, 3] tensors on this renderer's GPU.  first_ray: ray i draws the rough-reflection
+        stream of pixel first_ray + i.  out: such a dict to write into, any subset of the keys that holds rgba
+        (tensors of at least n rows; the rest is left alone): only those are written and returned; else five new
+        tensors.  counts: an int64 [2] tensor the kernel adds to: [0] the call's shadow rays, [1] its reflection
+        rays (what stats() reports after trace_ray)."""
+        import torch
+        op, dp, n = _lib.device_ray_args(orig, dirs, self.device, ("orig", "dirs"))
+        if n > 1 << 30:
+            raise ValueError(f"trace_ray_device: {n} rays, at most 2^30 are taken")
+        stream = self._ray_stream(stream)
+        if out is None:
+            with torch.cuda.stream(stream):
+                out = {k: torch.empty((n, c) if c else n, dtype=getattr(torch, dt), device=orig.device)
+                       for k, dt, c in _lib.SHADE_OUT}
+        ptrs = _lib.device_shade_outs(out, n, self.device)
+        cp = None if counts is None else _lib.device_ray_out(counts, "counts", torch.int64, 2, self.device)
+        self._call("rt_trace_ray_device", C.c_void_p(op), C.c_void_p(dp), n, int(current_recursion_depth),
+                   int(first_ray), *[C.c_void_p(p) for p in ptrs], C.c_void_p(cp),
+                   self._stream_ptr(stream, self.device))
+        return out
+
+    def device_shaded_queries(self):
+        """rt_get_device_shaded_queries -> (calls, rays): launches of trace_ray_device's plain, generic and
+        reflective kernel instance since the renderer was created, and the rays given to them (three ints
+        each)."""
+        calls, rays = np.zeros(3, np.int64), np.zeros(3, np.int64)
+        i64p = C.POINTER(C.c_int64)
+        self._call("rt_get_device_shaded_queries", ptr(calls, i64p), ptr(rays, i64p))
+        return tuple(int(c) for c in calls), tuple(int(r) for r in rays)
+
     def wide_query(self, orig, dirs, kind=1):
         """rt_wide_query: the frames' wide-BVH query on the GPU with its status -> dict(o, d, status,
         id, t, u, v, shadowed); kind 0 plain rays, 1 camera rays, 2 (hit point, normal) pairs as

@@ -8,6 +8,14 @@ Rows, all in one process:
                  upload, the download and the host wait are inside it: they are part of that call)
   device_octree  trace_rays_device / is_shadowed_device of a second renderer created with RT_WBVH=0
   device         the same calls of the default renderer
+Shaded rows on sets (a) and (b), likewise (rt_trace_ray / rt_trace_ray_device):
+  host            Renderer.trace_ray from numpy arrays
+  device_generic  trace_ray_device of a renderer created with RT_SHADE_PLAIN=0 (the generic instance)
+  device          trace_ray_device of the default renderer (C4 is a plain scene: the plain instance)
+and, on C5's settings (sphere1m_refl: rough reflections, 16 samples, depth 5), 2^18 camera rays of set (a): host
+against device (the reflective instance, the per-lane recursion).  Their counts are the call's shadow and
+reflection rays.  The shaded rows of one set must agree in sources, t and flags bit for bit and in RGBA within
+RGBA_TOL (the plain instance shades through the frames' expressions), and the counts must be the host row's.
 Each call is timed with a torch.cuda.Event pair on the call's stream, after a warm-up of the same shape;
 the median and the range of the repetitions are reported, with Mrays/s from the median and the counts
 trace_rays_device adds up (rays answered by the wide query, rays traced through the octree).  The outputs
@@ -29,6 +37,8 @@ from raytracercpp_amd.renderer import Renderer, render
 reps = max(10, int(sys.argv[1])) if len(sys.argv) > 1 else 10
 n = 1 << (int(sys.argv[2]) if len(sys.argv) > 2 else 22)
 KEYS = ("tri_id", "t", "u", "v", "ret")
+SHADE_KEYS = ("rgba", "hit_src", "t", "intersection_found", "shadowed")
+RGBA_TOL = 1e-4   # the project's (tests/test_trace_ray.py)
 dev = torch.device("cuda", 0)   # (no GPU: this raises at the first tensor)
 gen = torch.Generator(device=dev)
 gen.manual_seed(20261020)
@@ -86,15 +96,17 @@ def timed(call):
 
 def report(ray_set, row, count, ms, counts=None):
     med = statistics.median(ms)
+    rate = count / med / 1e3   # (one decimal, or four digits of a rate below 100: the C5 rows run at 0.016)
     line = {"set": ray_set, "row": row, "rays": count, "ms_median": round(med, 4), "ms_min": round(min(ms), 4),
-            "ms_max": round(max(ms), 4), "reps": len(ms), "mrays_per_s": round(count / med / 1e3, 1)}
+            "ms_max": round(max(ms), 4), "reps": len(ms), "mrays_per_s": round(rate, 1) if rate >= 100 else float("%.4g" % rate)}
     if counts is not None:
         line["counts"] = counts
     print(json.dumps(line), flush=True)
     return line
 
 
-def make(env=None):
+def make(env=None, scene=None):
+    sc, st = scene or (globals()["sc"], globals()["st"])
     old = {k: os.environ.get(k) for k in (env or {})}
     os.environ.update(env or {})
     try:
@@ -119,8 +131,54 @@ if not have:
 renderers = {"device": make()}
 if have:
     renderers["device_octree"] = make({"RT_WBVH": "0"})
+have_shaded = have and all(_lib.has(s) for s in getattr(_lib, "SHADED_QUERIES", ("missing",)))
+if have_shaded:
+    renderers["device_generic"] = make({"RT_SHADE_PLAIN": "0"})
+else:
+    print("shaded rows: skipped (the library lacks the shaded device query)", flush=True)
 print(json.dumps({"scene": "sphere1m", "triangles": int(sc.ntri), "rays_per_set": n, "repetitions": reps,
                   "wide_tree": {k: r.stats()["wide_tree"] for k, r in renderers.items()}}), flush=True)
+
+
+def shaded_rows(ray_set, rows, o, d):
+    """The shaded rows of one ray set: rows = [(name, renderer)], the host row from the first renderer."""
+    global ok
+    count = int(o.shape[0])
+    oh, dh = o.cpu().numpy(), d.cpu().numpy()
+    torch.cuda.synchronize()
+    host = rows[0][1]
+    ref, ms = timed(lambda: host.trace_ray(oh, dh, 0))
+    hs = host.stats()
+    want = [hs["shadow_rays"], hs["reflection_rays"]]
+    lines.append(report(ray_set, "shaded host", count, ms, want))
+    ref = [torch.from_numpy(a).to(dev) for a in ref]
+    for row, r in rows:
+        out = {k: torch.empty_like(a) for k, a in zip(SHADE_KEYS, ref)}
+        counts = torch.zeros(2, dtype=torch.int64, device=dev)
+        calls0 = r.device_shaded_queries()[0]
+        _, ms = timed(lambda: r.trace_ray_device(o, d, out=out, counts=counts))
+        total = [int(x) for x in counts.cpu()]   # (the warm-up and the repetitions added to it)
+        c = [x // (reps + 1) for x in total]
+        line = report(ray_set, "shaded " + row, count, ms, c)
+        inst = [b - a for a, b in zip(calls0, r.device_shaded_queries()[0])]
+        err = float((out["rgba"] - ref[0]).abs().max())
+        nbits = int((out["rgba"].view(torch.int32) != ref[0].view(torch.int32)).any(1).sum())
+        print(json.dumps({"set": ray_set, "row": "shaded " + row, "launches_plain_generic_reflective": inst,
+                          "max_abs_rgba_diff_from_host": err, "rays_whose_rgba_bits_differ_from_host": nbits}), flush=True)
+        lines.append(line)
+        if total != [w * (reps + 1) for w in want]:
+            ok = False
+            print(f"set {ray_set}, row shaded {row}: counts {total} over {reps + 1} calls, the host row's {want} per call",
+                  flush=True)
+        if not err <= RGBA_TOL:
+            ok = False
+            print(f"set {ray_set}, row shaded {row}: RGBA differs from the host row by {err}", flush=True)
+        for k, a in zip(SHADE_KEYS[1:], ref[1:]):
+            if not torch.equal(as_bits(out[k]), as_bits(a)):
+                ok = False
+                print(f"set {ray_set}, row shaded {row}: {k} differs from the host row in "
+                      f"{int((as_bits(out[k]) != as_bits(a)).sum())} rays", flush=True)
+
 
 ok = True
 lines = []
@@ -129,6 +187,10 @@ for ray_set, maker in (("a", rays_camera), ("b", rays_box)):
     o, d = maker()
     oh, dh = o.cpu().numpy(), d.cpu().numpy()
     torch.cuda.synchronize()
+    if have_shaded:
+        shaded_rows(ray_set, [("device_generic", renderers["device_generic"]), ("device", renderers["device"])], o, d)
+    if ray_set == "a":
+        cam_rays = (o[: 1 << 18].contiguous(), d[: 1 << 18].contiguous())
     ref, ms = timed(lambda: renderers["device"].trace_rays(oh, dh))
     lines.append(report(ray_set, "host", n, ms))
     ref = [torch.from_numpy(a).to(dev) for a in ref]
@@ -162,5 +224,11 @@ if pairs is not None:
             print(f"set c: the rows differ in {int((first != sh).sum())} pairs", flush=True)
 for r in renderers.values():
     r.close()
+if have_shaded:
+    # C5's settings: the reflective instance (the per-lane recursion) against the host call
+    r5 = make(scene=scenes.sphere1m_refl())
+    print(json.dumps({"scene": "sphere1m_refl", "rays": 1 << 18, "wide_tree": {"device": r5.stats()["wide_tree"]}}), flush=True)
+    shaded_rows("a, C5 settings", [("device", r5)], *cam_rays)
+    r5.close()
 print(json.dumps({"equal": ok}), flush=True)
 sys.exit(0 if ok else 1)
