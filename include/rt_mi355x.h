@@ -503,6 +503,38 @@ int rt_trace_ray_device(rt_renderer *r, const float *d_orig, const float *d_dir,
                         int64_t *d_counts, void *hip_stream);
 int rt_get_device_shaded_queries(rt_renderer *r, int64_t calls[3], int64_t rays[3]);
 
+/* Shaded ray batches through the frame engine (no reference counterpart).
+ * rt_trace_ray_batch_device takes rt_trace_ray_device's arguments, in the same order and with the same meaning, and
+ * writes per ray what that call writes for the ray in the same renderer state: d_hit_src, d_t, d_found and
+ * d_shadowed bit for bit, d_counts[0..1] += the same shadow and reflection ray counts, d_rgba the colour the frame
+ * engine computes for the ray (for a frame's camera rays, bit for bit the float RGBA an engine frame of the same
+ * renderer writes; within the project's RGBA bar of the reference's trace_ray).  On a scene with a reflective
+ * material rt_trace_ray_device walks each ray's whole compute_reflection recursion in one lane; this call shades
+ * the batch level by level as the frames do, which is what a caller with many rays on a mirror or rough scene wants.
+ * The optional outputs, first_ray, current_recursion_depth (past max_recursion_depth: the fill kernel), the pointer
+ * check, every refusal and the scene's validation are rt_trace_ray_device's; n == 0: RT_OK, no launch.
+ * The contract differs from rt_trace_ray_device's:
+ *  - The work is ordered on hip_stream: it runs after what was queued there before the call, and what is queued
+ *    after the call sees the outputs.  But the host blocks during the call: the engine reads its per-chunk counts
+ *    back, at least once per level.  The last pass may still be in flight when the call returns.
+ *  - The call may allocate device memory: the engine's level buffers grow as for frames (shared with them).
+ *  - hip_stream first waits for band launches and ray queries in flight on other streams, and later band launches
+ *    and frames wait for this call, as for any launch that uses the engine's buffers.
+ *  - rt_get_stats, rt_band_counters and the image of a band launch around the call are what they are without it.
+ * The n rays are shaded in batches of 2^RT_SHADE_BATCH_LOG2 (read by rt_create; 10..24, default 22).
+ * Where the engine does not apply -- no reflective material, enable_bvh 0, RT_REFL_ENGINE=0 -- the call is
+ * rt_trace_ray_device: the same code path, the same bytes, that call's contract, and its counters move.
+ * No choice is made by n: for few rays, or rays that reflect once (a mirror), rt_trace_ray_device can be faster.
+ * rt_get_device_shaded_batches: calls[0] / rays[0] = the calls the engine shaded since rt_create and their rays,
+ * calls[1] / rays[1] = the calls handed to rt_trace_ray_device's code; the fill past the depth limit and an empty
+ * call count in neither. */
+int rt_trace_ray_batch_device(rt_renderer *r, const float *d_orig, const float *d_dir, int64_t n,
+                              int32_t current_recursion_depth, int64_t first_ray,
+                              float *d_rgba, int32_t *d_hit_src, float *d_t,
+                              uint8_t *d_found, uint8_t *d_shadowed,
+                              int64_t *d_counts, void *hip_stream);
+int rt_get_device_shaded_batches(rt_renderer *r, int64_t calls[2], int64_t rays[2]);
+
 /* Renderer::trace_ray(ray, hit_info, current_recursion_depth, intersection_found)
  * (renderer.h:144, renderer.cpp:1008-1066) for n arbitrary rays (origins / directions [n][3]),
  * each with a fresh HitInfo: rgba [n][4] = the Color trace_ray returns (shading, shadow ray,

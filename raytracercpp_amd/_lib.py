@@ -147,7 +147,10 @@ SIGNATURES = {
     "rt_trace_ray_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_get_device_shaded_queries": (C.c_int, [_H, _i64p, _i64p]),
-    "rt_trace_ray": (C.c_int, [_H, _f32p, _f32p, C.c_int64, C.c_int32, _f32p, _i32p, _f32p, _u8p, _u8p]),
+    "rt_trace_ray_batch_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_get_device_shaded_batches": (C.c_int, [_H, _i64p, _i64p]),
+    "rt_trace_ray":(C.c_int, [_H, _f32p, _f32p, C.c_int64, C.c_int32, _f32p, _i32p, _f32p, _u8p, _u8p]),
     "rt_wide_query": (C.c_int, [_H, _f32p, _f32p, C.c_int64, C.c_int32, _f32p, _f32p, _i32p, _i32p, _f32p, _f32p, _f32p,
                                 _u8p]),
     "rt_risk_words": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_uint64), C.c_int64, _i64p, _i64p]),
@@ -197,6 +200,8 @@ GEOMETRY_INPUT = ("rt_set_triangles_device", "rt_update_vertices_device", "rt_ge
 RAY_QUERIES = ("rt_trace_rays_device", "rt_is_shadowed_device", "rt_get_device_ray_queries")
 # the shaded device query, likewise
 SHADED_QUERIES = ("rt_trace_ray_device", "rt_get_device_shaded_queries")
+# the shaded batches through the frame engine, likewise
+SHADED_BATCHES = ("rt_trace_ray_batch_device", "rt_get_device_shaded_batches")
 # the tile lists' read-back, likewise (an A/B run against the parent commit's library)
 TILE_LISTS = ("rt_tile_lists",)
 
@@ -223,7 +228,8 @@ def lib():
             pass
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            if name in GEOMETRY_INPUT + RAY_QUERIES + SHADED_QUERIES + TILE_LISTS and os.environ.get("RT_LIB_PATH") and not hasattr(L, name):
+            if (name in GEOMETRY_INPUT + RAY_QUERIES + SHADED_QUERIES + SHADED_BATCHES + TILE_LISTS and
+                    os.environ.get("RT_LIB_PATH") and not hasattr(L, name)):
                 continue
             fn = getattr(L, name)
             fn.restype = res

@@ -499,6 +499,24 @@ int rt_get_device_shaded_queries(rt_renderer* r, int64_t calls[3], int64_t rays[
         return RT_OK;
     });
 }
+int rt_trace_ray_batch_device(rt_renderer* r, const float* d_orig, const float* d_dir, int64_t n,
+                              int32_t current_recursion_depth, int64_t first_ray, float* d_rgba, int32_t* d_hit_src,
+                              float* d_t, uint8_t* d_found, uint8_t* d_shadowed, int64_t* d_counts, void* hip_stream)
+{
+    return guarded(R(r), [&] {
+        return R(r)->trace_ray_batch_device(d_orig, d_dir, n, current_recursion_depth, first_ray, d_rgba, d_hit_src, d_t,
+                                            d_found, d_shadowed, d_counts, reinterpret_cast<hipStream_t>(hip_stream));
+    });
+}
+int rt_get_device_shaded_batches(rt_renderer* r, int64_t calls[2], int64_t rays[2])
+{
+    return guarded(R(r), [&] {
+        if (!calls || !rays)
+            return RT_EINVAL;
+        R(r)->device_shaded_batches(calls, rays);
+        return RT_OK;
+    });
+}
 int rt_wide_query(rt_renderer* r, const float* orig, const float* dir, int64_t n, int32_t kind, float* o_out,
                   float* d_out, int32_t* status, int32_t* tri_id, float* t, float* u, float* v, uint8_t* shadowed)
 {

@@ -3815,6 +3815,69 @@ __global__ __launch_bounds__(256) void shade_rays_fill_kernel(int n, float4* __r
     if (out_shadow) out_shadow[i] = 0;
 }
 
+// waves per SIMD of refl_rays_level0_kernel: at RT_OCC (5, 96 VGPRs) it spilled 92 VGPRs (1,480 B of scratch), at
+// 4 (128) 9 (1,304 B), at the plain kernel's 3 it takes 137 and spills none (1,272 B, the out-of-line calls'
+// frames): the bound closest_rays_kernel took for the same reason
+#ifndef RT_OCC_RAYS0
+#define RT_OCC_RAYS0 RT_OCC_PLAIN
+#endif
+
+// Level 0 of the frame engine for a batch of rays in the caller's device memory (rt_trace_ray_batch_device):
+// refl_level0_kernel's body, one lane per ray instead of a tile queue.  Ray i starts at orig / dir, draws the
+// rough-reflection stream of pixel first_ray + i, and its output offset and FrameRec::parent are i: the host
+// points P.rgba / P.hit_id / P.hit_t / P.shadow (and out_found) at the batch's first ray, so the engine's
+// resolve at level 1 writes a deferred ray's colour through P.rgba[parent].  P.argb, P.zbuf and P.nbuf are null.
+// (The host sends no batch past the depth limit here: P.max_recursion_depth >= 0.)  The shadow rays go to
+// P.counters[0] with one atomic per wave, so no lane leaves before the wave's sum.
+__global__ __launch_bounds__(BLOCK, RT_OCC_RAYS0) void refl_rays_level0_kernel(
+    KParams P_arg, const float* __restrict__ orig, const float* __restrict__ dir, int n, uint32_t first_ray,
+    FrameRec* fr1, unsigned int* nfr1, uint8_t* __restrict__ out_found)
+{
+    const KParams& P = kernel_params();
+    (void)P_arg;
+    uint2* lv = lane_stack();
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    unsigned nshadow = 0;
+    if (i < n) {
+        const size_t j = 3 * (size_t)i;   // (in 64 bits, as closest_rays_kernel)
+        const v3 ro = mk(orig[j], orig[j + 1], orig[j + 2]);
+        const v3 rd = mk(dir[j], dir[j + 1], dir[j + 2]);
+        Rec fin = rec_fresh();
+        const int src = closest_hit(P, ro, rd, fin, lv);
+        bool found = false, shadowed = false, deferred = false;
+        c3 color;
+        float alpha = 1.0f;
+        if (fin.t > 0.1f) {
+            found = true;
+            Direct D = shade_direct(P, ro, rd, fin, lv, nshadow);
+            shadowed = D.shadowed;
+            const float* m = mat_of(P, fin.mat);
+            if (m[12] > 0.0f) {
+                const unsigned idx = atomicAdd(nfr1, 1u);
+                // (first_ray + n <= 2^32, checked on the host)
+                make_frame(P, fr1[idx], D.ip, fin.normal, rd, D.fc, frame_roughness(P, fin, m), fin.mat,
+                           pixel_seed(first_ray + (uint32_t)i, P.rng_seed), i);
+                deferred = true;
+            } else
+                color = shade_finish(P, D.fc, m, col(0, 0, 0));
+        } else
+            color = miss_color(P, rd, alpha);
+        if (!deferred) P.rgba[i] = make_float4(color.r, color.g, color.b, alpha);
+        if (P.hit_id) P.hit_id[i] = found ? src : -1;
+        if (P.hit_t) P.hit_t[i] = fin.t;
+        if (out_found) out_found[i] = found ? 1 : 0;
+        if (P.shadow) P.shadow[i] = (uint8_t)(found && shadowed);
+    }
+    wave_count_add(&P.counters[0], nshadow);
+}
+
+// d_counts[0..1] += the engine's shadow and reflection ray counts of an rt_trace_ray_batch_device call
+__global__ void add_ray_counts_kernel(const unsigned long long* __restrict__ counters, unsigned long long* counts)
+{
+    if (threadIdx.x < 2)
+        atomicAdd(&counts[threadIdx.x], counters[threadIdx.x]);
+}
+
 // The wide BVH's triangle records and their metadata, gathered on the device from the octree's
 // (already uploaded) instead of uploading 64 B per triangle again: wide-BVH triangle k is octree
 // slot s = slot[k]; wmeta[k] = {s, its octree leaf, its caller index, that triangle's material}.
@@ -4028,6 +4091,24 @@ hipError_t rt_launch_shade_rays_fill(int n, float4* rgba, int32_t* src, float* t
         return hipSuccess;
     hipLaunchKernelGGL(rt::shade_rays_fill_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, rgba, src, t, found,
                        shadow);
+    return hipGetLastError();
+}
+
+hipError_t rt_launch_refl_rays_level0(const rt::KParams* P, const float* o, const float* d, int n, uint32_t first_ray,
+                                      rt::FrameRec* fr1, unsigned int* nfr1, uint8_t* found, hipStream_t stream)
+{
+    if (n <= 0)
+        return hipSuccess;
+    size_t lds = rt::lds_bytes(*P);
+    hipLaunchKernelGGL(rt::refl_rays_level0_kernel, dim3((n + rt::BLOCK - 1) / rt::BLOCK), dim3(rt::BLOCK), lds, stream,
+                       *P, o, d, n, first_ray, fr1, nfr1, found);
+    return hipGetLastError();
+}
+
+hipError_t rt_launch_add_ray_counts(const unsigned long long* counters, int64_t* counts, hipStream_t stream)
+{
+    hipLaunchKernelGGL(rt::add_ray_counts_kernel, dim3(1), dim3(64), 0, stream, counters,
+                       reinterpret_cast<unsigned long long*>(counts));
     return hipGetLastError();
 }
 

@@ -100,6 +100,12 @@ RT_LAUNCH rt_launch_gather_points(const float* verts, int64_t nv, const int32_t*
 
 // the reflection engine (renderer.cpp drives the levels)
 RT_LAUNCH rt_launch_refl_level0(const rt::KParams* P, rt::FrameRec* fr1, unsigned int* nfr1, hipStream_t stream);
+// level 0 over a batch of rays in the caller's device memory (rt_trace_ray_batch_device): P's outputs and found
+// point at the batch's first ray, ray i is keyed as pixel first_ray + i; then the call's counts, counts[0..1] +=
+// counters[0..1]
+RT_LAUNCH rt_launch_refl_rays_level0(const rt::KParams* P, const float* o, const float* d, int n, uint32_t first_ray,
+                                     rt::FrameRec* fr1, unsigned int* nfr1, uint8_t* found, hipStream_t stream);
+RT_LAUNCH rt_launch_add_ray_counts(const unsigned long long* counters, int64_t* counts, hipStream_t stream);
 RT_LAUNCH rt_launch_refl_stage(rt::ReflStage stage, const rt::KParams* P, const rt::ReflArgs* A, hipStream_t stream);
 RT_LAUNCH rt_launch_refl_keys(const rt::KParams* P, const rt::FrameRec* fr, int n, uint32_t* keys, int32_t* idx,
                               hipStream_t stream);

@@ -143,6 +143,9 @@ Knobs Knobs::from_env()
     const int chunk = num("RT_REFL_CHUNK_LOG2", k.refl_chunk_log2);
     if (chunk >= 10 && chunk <= 27)   // small values (tests): many chunks per level
         k.refl_chunk_log2 = chunk;
+    const int batch = num("RT_SHADE_BATCH_LOG2", k.shade_batch_log2);
+    if (batch >= 10 && batch <= 24)   // small values (tests): several batches per call
+        k.shade_batch_log2 = batch;
     return k;
 }
 
@@ -2848,34 +2851,150 @@ int Renderer::trace_ray_device(const float* d_orig, const float* d_dir, int64_t 
                                float* d_rgba, int32_t* d_src, float* d_t, uint8_t* d_found, uint8_t* d_shadow,
                                int64_t* d_counts, hipStream_t stream)
 {
+    return shade_rays_device("trace_ray_device", d_orig, d_dir, n, depth, first_ray, d_rgba, d_src, d_t, d_found, d_shadow,
+                             d_counts, stream);
+}
+
+int Renderer::begin_shaded_query(const char* what, const float* d_orig, const float* d_dir, int64_t n, int depth,
+                                 int64_t first_ray, float* d_rgba, int32_t* d_src, float* d_t, uint8_t* d_found,
+                                 uint8_t* d_shadow, int64_t* d_counts, hipStream_t stream, KParams& P, bool& launch)
+{
+    launch = false;
     // (ray i is keyed as pixel first_ray + i, a 32-bit pixel index; n is bounded first, so no sum overflows)
     if (depth < 0 || n < 0 || n > (1 << 30) || first_ray < 0 || first_ray > (1ll << 32) - n)
-        return fail(RT_EINVAL, "trace_ray_device: bad arguments");
+        return fail(RT_EINVAL, std::string(what) + ": bad arguments");
     if (reinterpret_cast<uintptr_t>(d_rgba) & 15u)
-        return fail(RT_EINVAL, "trace_ray_device: d_rgba is not 16-byte aligned");
+        return fail(RT_EINVAL, std::string(what) + ": d_rgba is not 16-byte aligned");
     const void* const ptrs[] = {d_orig, d_dir, d_rgba, d_src, d_t, d_found, d_shadow, d_counts};
-    KParams P;
     const bool past = depth > s_.max_recursion_depth;
-    int rc = begin_ray_query("trace_ray_device", ptrs, 8, 3, n, stream, P, true, !past);
+    int rc = begin_ray_query(what, ptrs, 8, 3, n, stream, P, true, !past);
     if (rc != RT_OK || n == 0)
         return rc;
-    hipError_t e;
     if (past) {
         // renderer.cpp:1012-1013: Color(0.0f), the record untouched, intersection_found false; no ray is traced
         // and nothing of the scene is read (no parameters, no risk words), so neither the counts nor the fence move
-        e = rt_launch_shade_rays_fill((int)n, reinterpret_cast<float4*>(d_rgba), d_src, d_t, d_found, d_shadow, stream);
+        hipError_t e =
+            rt_launch_shade_rays_fill((int)n, reinterpret_cast<float4*>(d_rgba), d_src, d_t, d_found, d_shadow, stream);
         return e != hipSuccess ? hip_fail(e, "shade_rays_fill_kernel launch") : RT_OK;
     }
     P.max_recursion_depth = s_.max_recursion_depth - depth;   // only the difference is read
+    launch = true;
+    return RT_OK;
+}
+
+int Renderer::shade_rays_device(const char* what, const float* d_orig, const float* d_dir, int64_t n, int depth,
+                                int64_t first_ray, float* d_rgba, int32_t* d_src, float* d_t, uint8_t* d_found,
+                                uint8_t* d_shadow, int64_t* d_counts, hipStream_t stream)
+{
+    KParams P;
+    bool launch;
+    int rc = begin_shaded_query(what, d_orig, d_dir, n, depth, first_ray, d_rgba, d_src, d_t, d_found, d_shadow, d_counts,
+                                stream, P, launch);
+    if (rc != RT_OK || !launch)
+        return rc;
     P.counters = nullptr;   // (the handle's counter words belong to the frames)
     const int inst = P.has_reflection                           ? SHADE_REFL
                      : P.plain && P.wnodes && knobs_.shade_plain ? SHADE_PLAIN
                                                                  : SHADE_GENERIC;
-    e = rt_launch_shade_rays(&P, inst, d_orig, d_dir, (int)n, (uint32_t)first_ray, reinterpret_cast<float4*>(d_rgba),
-                             d_src, d_t, d_found, d_shadow, d_counts, stream);
+    hipError_t e = rt_launch_shade_rays(&P, inst, d_orig, d_dir, (int)n, (uint32_t)first_ray,
+                                        reinterpret_cast<float4*>(d_rgba), d_src, d_t, d_found, d_shadow, d_counts, stream);
     if (e != hipSuccess)
         return hip_fail(e, "shade_rays_kernel launch");
     return end_ray_query(2 + inst, n, stream);
+}
+
+// trace_ray_device's arguments and per-ray results, shaded by the frame engine (rt_trace_ray_batch_device, DESIGN.md
+// 13).  A scene the engine does not render (no reflective material, enable_bvh 0, RT_REFL_ENGINE=0) goes to
+// trace_ray_device's own code.  Otherwise level 0 runs over the caller's rays (kernels.hip
+// refl_rays_level0_kernel), the reflective hits become level-1 frames, and refl_level does the rest as for a
+// frame, writing through P.rgba.  Unlike trace_ray_device the host waits (the engine reads its counts per level
+// and chunk), the level buffers may grow, and since they and d_counters_ are shared with the frames, the stream
+// first waits for band launches and queries in flight (wait_slots); query_fence_ follows the last resolve.
+// Nothing rt_get_stats or rt_band_counters read is written: last_shadow_ / last_refl_ stay, a band slot has
+// counter words of its own, and d_counters_ is cleared by every frame before it is used.
+int Renderer::trace_ray_batch_device(const float* d_orig, const float* d_dir, int64_t n, int depth, int64_t first_ray,
+                                     float* d_rgba, int32_t* d_src, float* d_t, uint8_t* d_found, uint8_t* d_shadow,
+                                     int64_t* d_counts, hipStream_t stream)
+{
+    static const char* const what = "trace_ray_batch_device";
+    // (KParams::has_reflection and launch_trace's choice, from the host's copies)
+    const bool engine = s_.shading_method == RT_SHADING && any_reflection(mats_) && s_.enable_bvh && knobs_.refl_engine;
+    if (!engine) {
+        int64_t launches = 0;
+        for (int k = 2; k < 5; k++)
+            launches -= query_calls_[k];
+        int rc = shade_rays_device(what, d_orig, d_dir, n, depth, first_ray, d_rgba, d_src, d_t, d_found, d_shadow,
+                                   d_counts, stream);
+        for (int k = 2; k < 5; k++)
+            launches += query_calls_[k];
+        if (rc == RT_OK && launches > 0) {   // (neither an empty call nor the fill)
+            query_calls_[6]++;
+            query_rays_[6] += n;
+        }
+        return rc;
+    }
+    KParams P;
+    bool launch;
+    int rc = begin_shaded_query(what, d_orig, d_dir, n, depth, first_ray, d_rgba, d_src, d_t, d_found, d_shadow, d_counts,
+                                stream, P, launch);
+    if (rc != RT_OK || !launch)
+        return rc;
+    rc = shade_batches(P, d_orig, d_dir, n, first_ray, d_rgba, d_src, d_t, d_found, d_shadow, d_counts, stream);
+    if (rc != RT_OK) {
+        // what was queued before the failure may still run: whatever replaces what it reads waits for it too
+        (void)query_fence_.record(stream, fence_stream_);
+        return rc;
+    }
+    return end_ray_query(5, n, stream);
+}
+
+int Renderer::shade_batches(KParams& P, const float* d_orig, const float* d_dir, int64_t n, int64_t first_ray,
+                            float* d_rgba, int32_t* d_src, float* d_t, uint8_t* d_found, uint8_t* d_shadow,
+                            int64_t* d_counts, hipStream_t stream)
+{
+    hipError_t e;
+    if ((e = d_counters_.reserve(NCOUNTER_WORDS * 8)) != hipSuccess)
+        return hip_fail(e, "hipMalloc (counters)");
+    if (wait_slots(stream) != RT_OK)   // band launches and queries in flight share the engine's buffers
+        return RT_EHIP;
+    if ((e = hipMemsetAsync(d_counters_.p, 0, NCOUNTER_WORDS * 8, stream)) != hipSuccess)
+        return hip_fail(e, "hipMemsetAsync");
+    P.counters = d_counters_.as<unsigned long long>();
+    P.argb = nullptr;
+    P.local_rows = 1;   // (refl_level1_begin sizes level 1 for rw x local_rows frames)
+    // Level 1 holds one FrameRec per ray of a batch and n goes up to 2^30.  The offsets are taken here, in 64
+    // bits: the kernels index ints within a batch.
+    const int64_t batch = (int64_t)1 << knobs_.shade_batch_log2;
+    for (int64_t b0 = 0; b0 < n; b0 += batch) {
+        const int nb = (int)std::min(batch, n - b0);
+        P.rw = nb;
+        P.rgba = reinterpret_cast<float4*>(d_rgba) + b0;
+        P.hit_id = d_src ? d_src + b0 : nullptr;
+        P.hit_t = d_t ? d_t + b0 : nullptr;
+        P.shadow = d_shadow ? d_shadow + b0 : nullptr;
+        int rc = refl_level1_begin(P, stream);
+        if (rc != RT_OK)
+            return rc;
+        ReflLevel& L1 = refl_[1];
+        // (first_ray + n <= 2^32: the key's pixel index fits 32 bits)
+        if ((e = rt_launch_refl_rays_level0(&P, d_orig + 3 * b0, d_dir + 3 * b0, nb, (uint32_t)(first_ray + b0),
+                                            L1.fr.as<FrameRec>(), L1.cnt.as<unsigned int>(), d_found ? d_found + b0 : nullptr,
+                                            stream)) != hipSuccess)
+            return hip_fail(e, "refl_rays_level0_kernel launch");
+        if ((rc = refl_level1_finish(P, stream, "refl_rays_level0_kernel", false)) != RT_OK)
+            return rc;
+    }
+    if (d_counts && (e = rt_launch_add_ray_counts(P.counters, d_counts, stream)) != hipSuccess)
+        return hip_fail(e, "add_ray_counts_kernel launch");
+    return RT_OK;
+}
+
+void Renderer::device_shaded_batches(int64_t calls[2], int64_t rays[2]) const
+{
+    for (int k = 0; k < 2; k++) {
+        calls[k] = query_calls_[5 + k];
+        rays[k] = query_rays_[5 + k];
+    }
 }
 
 void Renderer::device_shaded_queries(int64_t calls[3], int64_t rays[3]) const

@@ -117,6 +117,8 @@ struct Knobs {
     bool fused_ssaa = true;   // RT_FUSED_SSAA=0: band launches downscale in a separate pass (7)
     bool refl_engine = true;  // RT_REFL_ENGINE=0: the one-lane-per-pixel recursive kernel (9)
     int refl_chunk_log2 = 27; // RT_REFL_CHUNK_LOG2 (10..27): sample slots per engine chunk
+    int shade_batch_log2 = 22; // RT_SHADE_BATCH_LOG2 (10..24): rays per engine batch of rt_trace_ray_batch_device
+                              // (level 1 holds one FrameRec per ray of a batch; small values: tests)
     bool debug_waves = false; // RT_DEBUG_WAVES: per-wave records of diagnostic builds (rt_debug_read)
     bool exact = false;       // RT_EXACT=1 / rt_set_exact: wbvh and seg off
     bool risk = true;         // RT_WBVH_RISK=0: no per-frame grazing-risk bits (every child runs case (b), 5.6)
@@ -293,6 +295,16 @@ public:
                          hipStream_t stream);
     // its launches and rays since rt_create by instance: plain, generic, reflective (rt_get_device_shaded_queries)
     void device_shaded_queries(int64_t calls[3], int64_t rays[3]) const;
+    // trace_ray_device's arguments and per-ray results through the frame engine (rt_trace_ray_batch_device, DESIGN.md
+    // 13): a scene with a reflective material, the BVH and the engine on is shaded level by level in batches of
+    // 2^RT_SHADE_BATCH_LOG2 rays on the caller's stream; the host waits for the engine's counts, the call may
+    // allocate, and the stream first waits for band launches and queries in flight.  Any other scene: trace_ray_device.
+    int trace_ray_batch_device(const float* d_orig, const float* d_dir, int64_t n, int depth, int64_t first_ray,
+                               float* d_rgba, int32_t* d_src, float* d_t, uint8_t* d_found, uint8_t* d_shadow,
+                               int64_t* d_counts, hipStream_t stream);
+    // its calls and rays since rt_create: [0] through the engine, [1] handed to trace_ray_device
+    // (rt_get_device_shaded_batches)
+    void device_shaded_batches(int64_t calls[2], int64_t rays[2]) const;
     // the frames' wide-BVH query and its status over n host rays (rt_wide_query)
     int wide_query(const float* orig, const float* dir, int64_t n, int kind, float* o_out, float* d_out,
                    int32_t* status, int32_t* id, float* t, float* u, float* v, uint8_t* shadow);
@@ -343,15 +355,30 @@ private:
     // The device ray queries (trace_rays_device, is_shadowed_device, trace_ray_device).  query_fence_ follows the
     // last launch on any stream: fence_stream_ runs in order, so the last record() comes after every earlier one.
     Fence query_fence_;
-    int64_t query_calls_[5] = {}, query_rays_[5] = {};   // closest hit, shadow, shaded: plain, generic, reflective
+    // closest hit, shadow, shaded: plain, generic, reflective, shaded batches: through the engine, delegated
+    int64_t query_calls_[7] = {}, query_rays_[7] = {};
     // before a query launch on 'stream': the count and the pointers (n_required of them must not be null when
     // n > 0; each must be memory of device_), the scene as a frame brings it up to date (shaded: validated as
     // trace_ray_colors validates it first), P with its risk words (reads_scene false: neither; the launch reads
     // nothing of the scene)
     int begin_ray_query(const char* what, const void* const* ptrs, int nptrs, int n_required, int64_t n,
                         hipStream_t stream, KParams& P, bool shaded = false, bool reads_scene = true);
-    // after it: the fence and the counters (kind 0 closest hit, 1 shadow, 2 + the shaded query's instance)
+    // after it: the fence and the counters (kind 0 closest hit, 1 shadow, 2 + the shaded query's instance, 5 a
+    // shaded batch through the engine)
     int end_ray_query(int kind, int64_t n, hipStream_t stream);
+    // The start the two shaded device queries share ('what': the caller's name in the error texts): the argument
+    // checks, begin_ray_query, and past the depth limit the fill.  launch: rays are left for the caller to shade
+    int begin_shaded_query(const char* what, const float* d_orig, const float* d_dir, int64_t n, int depth,
+                           int64_t first_ray, float* d_rgba, int32_t* d_src, float* d_t, uint8_t* d_found,
+                           uint8_t* d_shadow, int64_t* d_counts, hipStream_t stream, KParams& P, bool& launch);
+    // trace_ray_device under the caller's name
+    int shade_rays_device(const char* what, const float* d_orig, const float* d_dir, int64_t n, int depth,
+                          int64_t first_ray, float* d_rgba, int32_t* d_src, float* d_t, uint8_t* d_found,
+                          uint8_t* d_shadow, int64_t* d_counts, hipStream_t stream);
+    // trace_ray_batch_device's engine passes over the batches (the fence follows, whatever they return)
+    int shade_batches(KParams& P, const float* d_orig, const float* d_dir, int64_t n, int64_t first_ray, float* d_rgba,
+                      int32_t* d_src, float* d_t, uint8_t* d_found, uint8_t* d_shadow, int64_t* d_counts,
+                      hipStream_t stream);
 
     Knobs knobs_;
     int device_;

@@ -482,10 +482,15 @@ class Renderer:
         (tensors of at least n rows; the rest is left alone): only those are written and returned; else five new
         tensors.  counts: an int64 [2] tensor the kernel adds to: [0] the call's shadow rays, [1] its reflection
         rays (what stats() reports after trace_ray)."""
+        return self._shade_device("rt_trace_ray_device", "trace_ray_device", orig, dirs, current_recursion_depth,
+                                  first_ray, out, counts, stream)
+
+    def _shade_device(self, fn, name, orig, dirs, depth, first_ray, out, counts, stream):
+        """The two shaded device queries' common form: the tensors' checks, new outputs on ``stream``, the call."""
         import torch
         op, dp, n = _lib.device_ray_args(orig, dirs, self.device, ("orig", "dirs"))
         if n > 1 << 30:
-            raise ValueError(f"trace_ray_device: {n} rays, at most 2^30 are taken")
+            raise ValueError(f"{name}: {n} rays, at most 2^30 are taken")
         stream = self._ray_stream(stream)
         if out is None:
             with torch.cuda.stream(stream):
@@ -493,10 +498,27 @@ class Renderer:
                        for k, dt, c in _lib.SHADE_OUT}
         ptrs = _lib.device_shade_outs(out, n, self.device)
         cp = None if counts is None else _lib.device_ray_out(counts, "counts", torch.int64, 2, self.device)
-        self._call("rt_trace_ray_device", C.c_void_p(op), C.c_void_p(dp), n, int(current_recursion_depth),
-                   int(first_ray), *[C.c_void_p(p) for p in ptrs], C.c_void_p(cp),
-                   self._stream_ptr(stream, self.device))
+        self._call(fn, C.c_void_p(op), C.c_void_p(dp), n, int(depth), int(first_ray), *[C.c_void_p(p) for p in ptrs],
+                   C.c_void_p(cp), self._stream_ptr(stream, self.device))
         return out
+
+    def trace_ray_batch_device(self, orig, dirs, current_recursion_depth=0, first_ray=0, out=None, counts=None,
+                               stream=None):
+        """rt_trace_ray_batch_device: trace_ray_device's arguments and answers, shaded by the frame engine where the
+        scene has a reflective material (level by level, as the frames; else it is trace_ray_device).  The work is
+        ordered on ``stream``, but the host blocks while the engine reads its counts, the call may allocate, and
+        the stream first waits for band launches and queries in flight.  hit_src, t, the flags and the counts are
+        trace_ray_device's bit for bit; rgba is the engine's colour (a frame's, for its camera rays)."""
+        return self._shade_device("rt_trace_ray_batch_device", "trace_ray_batch_device", orig, dirs,
+                                  current_recursion_depth, first_ray, out, counts, stream)
+
+    def device_shaded_batches(self):
+        """rt_get_device_shaded_batches -> (calls, rays): trace_ray_batch_device's calls the engine shaded [0] and
+        those handed to trace_ray_device's code [1] since the renderer was created, and their rays."""
+        calls, rays = np.zeros(2, np.int64), np.zeros(2, np.int64)
+        i64p = C.POINTER(C.c_int64)
+        self._call("rt_get_device_shaded_batches", ptr(calls, i64p), ptr(rays, i64p))
+        return tuple(int(c) for c in calls), tuple(int(r) for r in rays)
 
     def device_shaded_queries(self):
         """rt_get_device_shaded_queries -> (calls, rays): launches of trace_ray_device's plain, generic and

@@ -14,18 +14,31 @@ Shaded rows on sets (a) and (b), likewise (rt_trace_ray / rt_trace_ray_device):
   device          trace_ray_device of the default renderer (C4 is a plain scene: the plain instance)
 and, on C5's settings (sphere1m_refl: rough reflections, 16 samples, depth 5), 2^18 camera rays of set (a): host
 against device (the reflective instance, the per-lane recursion).  Their counts are the call's shadow and
-reflection rays.  The shaded rows of one set must agree in sources, t and flags bit for bit and in RGBA within
+reflection rays.
+Batch rows (rt_trace_ray_batch_device, the frame engine), one per shaded ray set, against the device row run in
+the same call:
+  batch           trace_ray_batch_device of the default renderer (C4 has no reflective material: the call is
+                  trace_ray_device's code there)
+On C5's settings the same 2^18 camera rays (section c5: device and batch alone, without the host row), then the
+sweep (section sweep): 2^10, 2^14 and 2^22 of set (a)'s rays on C5's settings (the device row only up to 2^14 and
+with 3 repetitions where one call takes more than 5 s: 2^22 rays would take it minutes per call), and 2^10 ...
+2^22 rays on the mirror golden's settings (roughness 0: one sample per hit, depth 5, no maps) over the same
+geometry, both rows.  A batch row must agree with its device row in sources, t, flags and counts bit for bit and
+in RGBA within RGBA_TOL; the rays whose RGBA bits differ are counted, and each pair of rows reports the ratio of
+the medians and whether the batch row's whole range lies below the device row's.  The shaded rows of one set must agree in sources, t and flags bit for bit and in RGBA within
 RGBA_TOL (the plain instance shades through the frames' expressions), and the counts must be the host row's.
 Each call is timed with a torch.cuda.Event pair on the call's stream, after a warm-up of the same shape;
 the median and the range of the repetitions are reported, with Mrays/s from the median and the counts
 trace_rays_device adds up (rays answered by the wide query, rays traced through the octree).  The outputs
 of all rows of one set must be equal bit for bit, else the tool exits with status 1.  Rows whose calls the
 loaded library lacks are skipped (RT_LIB_PATH naming an older build: the host row alone).
-Usage: python tools/ray_query_time.py [repetitions [log2 rays]]"""
+Usage: python tools/ray_query_time.py [repetitions [log2 rays [sections]]]
+sections: a comma list of c4 (sets a, b, c), c5host (C5 with the host row), c5, sweep; default all of them."""
 import json
 import os
 import statistics
 import sys
+import time
 
 import numpy as np
 import torch
@@ -36,6 +49,10 @@ from raytracercpp_amd.renderer import Renderer, render
 
 reps = max(10, int(sys.argv[1])) if len(sys.argv) > 1 else 10
 n = 1 << (int(sys.argv[2]) if len(sys.argv) > 2 else 22)
+SECTIONS = ("c4", "c5host", "c5", "sweep")
+sections = tuple(sys.argv[3].split(",")) if len(sys.argv) > 3 else SECTIONS
+if set(sections) - set(SECTIONS):
+    sys.exit("sections: a comma list of " + ", ".join(SECTIONS))
 KEYS = ("tri_id", "t", "u", "v", "ret")
 SHADE_KEYS = ("rgba", "hit_src", "t", "intersection_found", "shadowed")
 RGBA_TOL = 1e-4   # the project's (tests/test_trace_ray.py)
@@ -79,10 +96,14 @@ def shadow_pairs(o, d, out):
     return p.contiguous(), nrm[ok].contiguous()
 
 
-def timed(call):
-    """The call's results and its durations in ms (one warm-up, then `reps` repetitions between event pairs)."""
+def timed(call, reps=reps, slow_ms=None, slow_reps=3):
+    """The call's results and its durations in ms (one warm-up, then `reps` repetitions between event pairs;
+    slow_ms: `slow_reps` repetitions when the warm-up took longer than that)."""
+    t0 = time.perf_counter()
     res = call()
     torch.cuda.synchronize()
+    if slow_ms is not None and (time.perf_counter() - t0) * 1e3 > slow_ms:
+        reps = slow_reps
     ms = []
     for _ in range(reps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -128,16 +149,67 @@ def as_bits(t):
 have = all(_lib.has(s) for s in _lib.RAY_QUERIES) if hasattr(_lib, "RAY_QUERIES") else False
 if not have:
     print("device, device_octree: skipped (the library lacks the device ray queries)", flush=True)
-renderers = {"device": make()}
-if have:
-    renderers["device_octree"] = make({"RT_WBVH": "0"})
 have_shaded = have and all(_lib.has(s) for s in getattr(_lib, "SHADED_QUERIES", ("missing",)))
-if have_shaded:
-    renderers["device_generic"] = make({"RT_SHADE_PLAIN": "0"})
-else:
-    print("shaded rows: skipped (the library lacks the shaded device query)", flush=True)
-print(json.dumps({"scene": "sphere1m", "triangles": int(sc.ntri), "rays_per_set": n, "repetitions": reps,
-                  "wide_tree": {k: r.stats()["wide_tree"] for k, r in renderers.items()}}), flush=True)
+have_batches = have_shaded and all(_lib.has(s) for s in getattr(_lib, "SHADED_BATCHES", ("missing",)))
+renderers = {}
+if "c4" in sections:
+    renderers["device"] = make()
+    if have:
+        renderers["device_octree"] = make({"RT_WBVH": "0"})
+    if have_shaded:
+        renderers["device_generic"] = make({"RT_SHADE_PLAIN": "0"})
+    else:
+        print("shaded rows: skipped (the library lacks the shaded device query)", flush=True)
+    if not have_batches:
+        print("batch rows: skipped (the library lacks the shaded batches)", flush=True)
+    print(json.dumps({"scene": "sphere1m", "triangles": int(sc.ntri), "rays_per_set": n, "repetitions": reps,
+                      "wide_tree": {k: r.stats()["wide_tree"] for k, r in renderers.items()}}), flush=True)
+
+
+def batch_rows(ray_set, r, o, d, device=True, ref=None, slow_ms=None):
+    """The device row (trace_ray_device; device False: none, the batch row alone) and the batch row
+    (trace_ray_batch_device) of renderer r over one ray set, compared with each other (ref: the device row's
+    outputs and counts when shaded_rows has run it already; slow_ms: the device row takes 3 repetitions when
+    one call takes longer than that)."""
+    global ok
+    count = int(o.shape[0])
+    new = lambda: {k: torch.empty((count, 4) if k == "rgba" else count, dtype=dt, device=dev)   # noqa: E731
+                   for k, dt in zip(SHADE_KEYS, (torch.float32, torch.int32, torch.float32, torch.uint8, torch.uint8))}
+    dms = None
+    if device and ref is None:
+        out, counts = new(), torch.zeros(2, dtype=torch.int64, device=dev)
+        _, dms = timed(lambda: r.trace_ray_device(o, d, out=out, counts=counts), slow_ms=slow_ms)
+        ref = (out, [int(x) // (len(dms) + 1) for x in counts.cpu()], dms)
+        lines.append(report(ray_set, "shaded device", count, dms, ref[1]))
+    elif ref is not None:
+        dms = ref[2]
+    out, counts = new(), torch.zeros(2, dtype=torch.int64, device=dev)
+    before = r.device_shaded_batches()
+    _, ms = timed(lambda: r.trace_ray_batch_device(o, d, out=out, counts=counts))
+    c = [int(x) // (len(ms) + 1) for x in counts.cpu()]
+    lines.append(report(ray_set, "shaded batch", count, ms, c))
+    after = r.device_shaded_batches()
+    note = {"set": ray_set, "row": "shaded batch",
+            "calls_engine_delegated": [b - a for a, b in zip(before[0], after[0])]}
+    if ref is not None:
+        err = float((out["rgba"] - ref[0]["rgba"]).abs().max())
+        note["max_abs_rgba_diff_from_device"] = err
+        note["rays_whose_rgba_bits_differ_from_device"] = int(
+            (out["rgba"].view(torch.int32) != ref[0]["rgba"].view(torch.int32)).any(1).sum())
+        note["device_over_batch_medians"] = round(statistics.median(dms) / statistics.median(ms), 2)
+        note["batch_range_below_device_range"] = max(ms) < min(dms)
+        if c != ref[1]:
+            ok = False
+            print(f"set {ray_set}, row shaded batch: counts {c}, the device row's {ref[1]}", flush=True)
+        if not err <= RGBA_TOL:
+            ok = False
+            print(f"set {ray_set}, row shaded batch: RGBA differs from the device row by {err}", flush=True)
+        for k in SHADE_KEYS[1:]:
+            if not torch.equal(as_bits(out[k]), as_bits(ref[0][k])):
+                ok = False
+                print(f"set {ray_set}, row shaded batch: {k} differs from the device row in "
+                      f"{int((as_bits(out[k]) != as_bits(ref[0][k])).sum())} rays", flush=True)
+    print(json.dumps(note), flush=True)
 
 
 def shaded_rows(ray_set, rows, o, d):
@@ -152,6 +224,7 @@ def shaded_rows(ray_set, rows, o, d):
     want = [hs["shadow_rays"], hs["reflection_rays"]]
     lines.append(report(ray_set, "shaded host", count, ms, want))
     ref = [torch.from_numpy(a).to(dev) for a in ref]
+    last = None
     for row, r in rows:
         out = {k: torch.empty_like(a) for k, a in zip(SHADE_KEYS, ref)}
         counts = torch.zeros(2, dtype=torch.int64, device=dev)
@@ -160,6 +233,7 @@ def shaded_rows(ray_set, rows, o, d):
         total = [int(x) for x in counts.cpu()]   # (the warm-up and the repetitions added to it)
         c = [x // (reps + 1) for x in total]
         line = report(ray_set, "shaded " + row, count, ms, c)
+        last = (out, c, ms)
         inst = [b - a for a, b in zip(calls0, r.device_shaded_queries()[0])]
         err = float((out["rgba"] - ref[0]).abs().max())
         nbits = int((out["rgba"].view(torch.int32) != ref[0].view(torch.int32)).any(1).sum())
@@ -178,19 +252,25 @@ def shaded_rows(ray_set, rows, o, d):
                 ok = False
                 print(f"set {ray_set}, row shaded {row}: {k} differs from the host row in "
                       f"{int((as_bits(out[k]) != as_bits(a)).sum())} rays", flush=True)
+    if have_batches:   # (the batch row against the last row above, the default renderer's)
+        batch_rows(ray_set, rows[-1][1], o, d, ref=last)
 
 
 ok = True
 lines = []
 pairs = None
+cam_all = None
 for ray_set, maker in (("a", rays_camera), ("b", rays_box)):
     o, d = maker()
+    if ray_set == "a":
+        cam_all = (o, d)
+        cam_rays = (o[: 1 << 18].contiguous(), d[: 1 << 18].contiguous())
+    if "c4" not in sections:
+        continue
     oh, dh = o.cpu().numpy(), d.cpu().numpy()
     torch.cuda.synchronize()
     if have_shaded:
         shaded_rows(ray_set, [("device_generic", renderers["device_generic"]), ("device", renderers["device"])], o, d)
-    if ray_set == "a":
-        cam_rays = (o[: 1 << 18].contiguous(), d[: 1 << 18].contiguous())
     ref, ms = timed(lambda: renderers["device"].trace_rays(oh, dh))
     lines.append(report(ray_set, "host", n, ms))
     ref = [torch.from_numpy(a).to(dev) for a in ref]
@@ -224,11 +304,32 @@ if pairs is not None:
             print(f"set c: the rows differ in {int((first != sh).sum())} pairs", flush=True)
 for r in renderers.values():
     r.close()
-if have_shaded:
-    # C5's settings: the reflective instance (the per-lane recursion) against the host call
+if have_shaded and set(sections) & {"c5host", "c5", "sweep"}:
     r5 = make(scene=scenes.sphere1m_refl())
     print(json.dumps({"scene": "sphere1m_refl", "rays": 1 << 18, "wide_tree": {"device": r5.stats()["wide_tree"]}}), flush=True)
-    shaded_rows("a, C5 settings", [("device", r5)], *cam_rays)
+    if "c5host" in sections:
+        # C5's settings: the reflective instance (the per-lane recursion) against the host call, then the batch row
+        shaded_rows("a, C5 settings", [("device", r5)], *cam_rays)
+    elif "c5" in sections and have_batches:
+        batch_rows("a, C5 settings", r5, *cam_rays)
+    if "sweep" in sections and have_batches:
+        for lg in (10, 14, 22):
+            if (1 << lg) <= n:
+                batch_rows(f"a, C5 settings, 2^{lg} rays", r5, cam_all[0][: 1 << lg].contiguous(),
+                           cam_all[1][: 1 << lg].contiguous(), device=lg <= 14, slow_ms=5000.0)
     r5.close()
+    if "sweep" in sections and have_batches:
+        # the mirror golden's settings over C5's geometry: roughness 0 (one sample per reflective hit), depth 5, no maps
+        scm, stm = scenes.sphere1m_refl()
+        scm.materials[0, 13] = 0.0
+        stm = stm.copy(rough_reflections_sample_count=3, max_recursion_depth=5, enable_normal_mapping=False,
+                       enable_displacement_mapping=False)
+        rm = make(scene=(scm, stm))
+        print(json.dumps({"scene": "sphere1m_refl as a mirror", "wide_tree": {"device": rm.stats()["wide_tree"]}}), flush=True)
+        for lg in (10, 14, 18, 22):
+            if (1 << lg) <= n:
+                batch_rows(f"a, mirror settings, 2^{lg} rays", rm, cam_all[0][: 1 << lg].contiguous(),
+                           cam_all[1][: 1 << lg].contiguous())
+        rm.close()
 print(json.dumps({"equal": ok}), flush=True)
 sys.exit(0 if ok else 1)
