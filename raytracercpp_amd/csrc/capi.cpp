@@ -485,10 +485,9 @@ int rt_trace_ray_device(rt_renderer* r, const float* d_orig, const float* d_dir,
                         int32_t current_recursion_depth, int64_t first_ray, float* d_rgba, int32_t* d_hit_src, float* d_t,
                         uint8_t* d_found, uint8_t* d_shadowed, int64_t* d_counts, void* hip_stream)
 {
-    return guarded(R(r), [&] {
-        return R(r)->trace_ray_device(d_orig, d_dir, n, current_recursion_depth, first_ray, d_rgba, d_hit_src, d_t,
-                                      d_found, d_shadowed, d_counts, reinterpret_cast<hipStream_t>(hip_stream));
-    });
+    const rt::ShadeRays q{d_orig, d_dir, n, current_recursion_depth, first_ray, d_rgba, d_hit_src, d_t, d_found, d_shadowed,
+                          d_counts};
+    return guarded(R(r), [&] { return R(r)->trace_ray_device(q, reinterpret_cast<hipStream_t>(hip_stream)); });
 }
 int rt_get_device_shaded_queries(rt_renderer* r, int64_t calls[3], int64_t rays[3])
 {
@@ -503,10 +502,9 @@ int rt_trace_ray_batch_device(rt_renderer* r, const float* d_orig, const float* 
                               int32_t current_recursion_depth, int64_t first_ray, float* d_rgba, int32_t* d_hit_src,
                               float* d_t, uint8_t* d_found, uint8_t* d_shadowed, int64_t* d_counts, void* hip_stream)
 {
-    return guarded(R(r), [&] {
-        return R(r)->trace_ray_batch_device(d_orig, d_dir, n, current_recursion_depth, first_ray, d_rgba, d_hit_src, d_t,
-                                            d_found, d_shadowed, d_counts, reinterpret_cast<hipStream_t>(hip_stream));
-    });
+    const rt::ShadeRays q{d_orig, d_dir, n, current_recursion_depth, first_ray, d_rgba, d_hit_src, d_t, d_found, d_shadowed,
+                          d_counts};
+    return guarded(R(r), [&] { return R(r)->trace_ray_batch_device(q, reinterpret_cast<hipStream_t>(hip_stream)); });
 }
 int rt_get_device_shaded_batches(rt_renderer* r, int64_t calls[2], int64_t rays[2])
 {

@@ -3709,40 +3709,6 @@ __global__ __launch_bounds__(BLOCK, RT_OCC_PLAIN) void shadow_points_kernel(KPar
     out_sh[i] = is_shadowed<false, 1, false, false, 1>(P, p, nrm, mk(lx, ly, lz), lv) ? 1 : 0;
 }
 
-// Renderer::trace_ray (renderer.cpp:1008-1066) for a batch of arbitrary rays, one lane per
-// ray, each with a fresh HitInfo: the colour trace_ray returns (shading, shadow ray, the
-// compute_reflection recursion when REFL), and the record it leaves.  The host folds
-// current_recursion_depth into P.max_recursion_depth (only their difference is read).  Ray
-// i's rough-reflection stream is keyed as pixel i of a frame.
-template <bool REFL>
-__global__ __launch_bounds__(BLOCK, RT_OCC) void trace_colors_kernel(KParams P_arg, const float* __restrict__ orig,
-                                                                     const float* __restrict__ dir, int n,
-                                                                     float4* __restrict__ out_rgba,
-                                                                     int32_t* __restrict__ out_src,
-                                                                     float* __restrict__ out_t,
-                                                                     uint8_t* __restrict__ out_found,
-                                                                     uint8_t* __restrict__ out_shadow)
-{
-    const KParams& P = kernel_params();
-    (void)P_arg;
-    uint2* lv = lane_stack();
-    const int i = blockIdx.x * BLOCK + threadIdx.x;
-    unsigned nshadow = 0, nrefl = 0;
-    if (i < n) {
-        const v3 o = mk(orig[3 * i], orig[3 * i + 1], orig[3 * i + 2]);
-        const v3 d = mk(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]);
-        const uint32_t key = REFL ? pixel_seed((uint32_t)i, P.rng_seed) : 0u;
-        PixelOut po = trace_pixel<REFL>(P, o, d, lv, key, nshadow, nrefl);
-        out_rgba[i] = make_float4(po.color.r, po.color.g, po.color.b, po.alpha);
-        out_src[i] = po.found ? po.src : -1;
-        out_t[i] = po.fin.t;
-        out_found[i] = po.found ? 1 : 0;
-        out_shadow[i] = (uint8_t)(po.found && po.shadowed);
-    }
-    if (nshadow) atomicAdd(&P.counters[0], (unsigned long long)nshadow);
-    if (nrefl) atomicAdd(&P.counters[1], (unsigned long long)nrefl);
-}
-
 // wave_count_add over 64 bits: the lanes' counts are 32-bit (trace_pixel's), and 64 of them need not fit 32 bits
 // together (a lane makes up to 16 + 16^2 + ... + 16^d reflection rays at 16 samples and depth d: 1.1 M at depth
 // 5, 72 M a wave, but 2^28 a lane from depth 7).  Every lane of the wave calls it.
@@ -3754,16 +3720,18 @@ __device__ __forceinline__ void wave_count_add64(unsigned long long* ctr, unsign
         atomicAdd(ctr, v);
 }
 
-// Renderer::trace_ray for a batch of rays that lie in the caller's device memory (rt_trace_ray_device): per ray
-// what trace_colors_kernel writes, one lane per ray.  Ray i draws the rough-reflection stream of pixel
-// first_ray + i.  Every output but the colour may be null; counts (optional): [0] += the call's shadow rays,
-// [1] += its reflection rays, one atomic per wave and word, so no lane leaves before the wave's sums.  It reads
-// nothing the frames write: no P.counters, no buffer of the handle's.
+// Renderer::trace_ray (renderer.cpp:1008-1066) for a batch of arbitrary rays in device memory, one lane per ray,
+// each with a fresh HitInfo (rt_trace_ray_device on the caller's arrays, rt_trace_ray on its staged copy): the
+// colour trace_ray returns (shading, shadow ray, the compute_reflection recursion in SHADE_REFL) and the record
+// it leaves.  The host folds current_recursion_depth into P.max_recursion_depth (only their difference is read).
+// Ray i draws the rough-reflection stream of pixel first_ray + i.  Every output but the colour may be null; counts
+// (optional): [0] += the call's shadow rays, [1] += its reflection rays, one atomic per wave and word, so no
+// lane leaves before the wave's sums.  It reads nothing the frames write: no P.counters, no buffer of the handle's.
 // INST: SHADE_PLAIN -- the frames' plain pixel (trace_pixel<false, true>: the colour through shade_lit /
 // shade_shadow_emit / shade_finish, the pixel's values in LDS across the shadow query) at the plain kernel's
 // occupancy, for a scene with P.plain over a resident wide BVH; its rays start at the root (no entry set: they
-// are not a block's camera rays).  SHADE_GENERIC / SHADE_REFL: trace_colors_kernel's own two instances of
-// trace_pixel, the same expressions and so the same bytes.
+// are not a block's camera rays).  SHADE_GENERIC / SHADE_REFL: the general trace_pixel without and with
+// reflections, the two rt_trace_ray takes, whose bytes are the reference for the other paths.
 template <int INST>
 __global__ __launch_bounds__(BLOCK, INST == SHADE_PLAIN ? RT_OCC_PLAIN : RT_OCC) void shade_rays_kernel(
     KParams P_arg, const float* __restrict__ orig, const float* __restrict__ dir, int n, uint32_t first_ray,
@@ -4046,22 +4014,6 @@ hipError_t rt_launch_shadow_points(const rt::KParams* P, const float* point, con
     size_t lds = rt::lds_bytes(*P);
     hipLaunchKernelGGL(rt::shadow_points_kernel, dim3((n + rt::BLOCK - 1) / rt::BLOCK), dim3(rt::BLOCK), lds, stream, *P,
                        point, normal, n, light[0], light[1], light[2], shadowed);
-    return hipGetLastError();
-}
-
-hipError_t rt_launch_trace_colors(const rt::KParams* P, bool refl, const float* o, const float* d, int n, float4* rgba,
-                                  int32_t* src, float* t, uint8_t* found, uint8_t* shadow, hipStream_t stream)
-{
-    if (n <= 0)
-        return hipSuccess;
-    size_t lds = rt::lds_bytes(*P);
-    dim3 grid((n + rt::BLOCK - 1) / rt::BLOCK), block(rt::BLOCK);
-    if (refl)
-        hipLaunchKernelGGL(rt::trace_colors_kernel<true>, grid, block, lds, stream, *P, o, d, n, rgba, src, t, found,
-                           shadow);
-    else
-        hipLaunchKernelGGL(rt::trace_colors_kernel<false>, grid, block, lds, stream, *P, o, d, n, rgba, src, t, found,
-                           shadow);
     return hipGetLastError();
 }
 

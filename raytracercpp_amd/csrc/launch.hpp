@@ -51,15 +51,13 @@ RT_LAUNCH rt_launch_closest_rays(const rt::KParams* P, const float* o, const flo
                                  float* u, float* v, uint8_t* ret, int64_t* counts, hipStream_t stream);
 RT_LAUNCH rt_launch_shadow_points(const rt::KParams* P, const float* point, const float* normal, int n,
                                   const float light[3], uint8_t* shadowed, hipStream_t stream);
-// the shaded query over the caller's device memory (rt_trace_ray_device): inst is rt::SHADE_*; every output but
-// rgba may be null; the fill writes what trace_ray returns past max_recursion_depth
+// the shaded query over device memory (rt_trace_ray_device; rt_trace_ray's staged arrays): inst is rt::SHADE_*;
+// every output but rgba may be null; the fill writes what trace_ray returns past max_recursion_depth
 RT_LAUNCH rt_launch_shade_rays(const rt::KParams* P, int inst, const float* o, const float* d, int n,
                                uint32_t first_ray, float4* rgba, int32_t* src, float* t, uint8_t* found,
                                uint8_t* shadow, int64_t* counts, hipStream_t stream);
 RT_LAUNCH rt_launch_shade_rays_fill(int n, float4* rgba, int32_t* src, float* t, uint8_t* found, uint8_t* shadow,
                                     hipStream_t stream);
-RT_LAUNCH rt_launch_trace_colors(const rt::KParams* P, bool refl, const float* o, const float* d, int n, float4* rgba,
-                                 int32_t* src, float* t, uint8_t* found, uint8_t* shadow, hipStream_t stream);
 RT_LAUNCH rt_launch_downscale(const uint32_t* in, int w, int h_rows, int f, uint32_t* out, hipStream_t stream);
 RT_LAUNCH rt_launch_ssao(const rt::SsaoArgs* A, hipStream_t stream);
 

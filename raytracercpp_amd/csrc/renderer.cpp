@@ -15,6 +15,7 @@
 #include "host_scene.hpp"
 #include "launch.hpp"
 #include "octree_gpu.hpp"
+#include "ray_stage.hpp"
 #include "wbvh_quick_gpu.hpp"
 
 namespace rt {
@@ -2721,6 +2722,37 @@ int Renderer::sync_slots()
     return RT_OK;
 }
 
+// The arrays of a host ray query (trace_rays, wide_query, trace_ray_colors) in one device allocation of the call's
+// own, laid out by ray_stage.hpp: upload() reserves it and copies the STAGE_UP arrays in, at<T>(k) is array k on
+// the device, download() copies the STAGE_DOWN arrays out and returns once they are in the caller's memory.  The
+// copies run on 'stream' from and to the caller's pageable arrays; nothing outlives the call.
+struct RayStage {
+    DevBuf buf;
+    const StageArray* a = nullptr;
+    int count = 0;
+    StageLayout L{};
+    template <class T> T* at(int k) const { return reinterpret_cast<T*>(buf.as<char>() + L.off[k]); }
+    hipError_t upload(const StageArray* arrays, int narrays, int64_t n, hipStream_t stream)
+    {
+        a = arrays;
+        count = narrays;
+        L = stage_layout(a, count, (uint64_t)n);
+        hipError_t e = buf.reserve((size_t)L.total);
+        for (int k = 0; k < count && e == hipSuccess; k++)
+            if (a[k].flags & STAGE_UP)
+                e = hipMemcpyAsync(at<char>(k), a[k].host, (size_t)L.bytes[k], hipMemcpyHostToDevice, stream);
+        return e;
+    }
+    hipError_t download(hipStream_t stream) const
+    {
+        hipError_t e = hipSuccess;
+        for (int k = 0; k < count && e == hipSuccess; k++)
+            if (a[k].flags & STAGE_DOWN)
+                e = hipMemcpyAsync(a[k].host, at<char>(k), (size_t)L.bytes[k], hipMemcpyDeviceToHost, stream);
+        return e != hipSuccess ? e : hipStreamSynchronize(stream);
+    }
+};
+
 int Renderer::trace_rays(const float* orig, const float* dir, int64_t n, int32_t* id, float* t, float* u, float* v,
                          uint8_t* ret)
 {
@@ -2733,30 +2765,21 @@ int Renderer::trace_rays(const float* orig, const float* dir, int64_t n, int32_t
         return RT_OK;
     KParams P;
     fill_params(P);
-    DevBuf din, dout;
-    size_t nb = (size_t)n;
-    hipError_t e;
-    if ((e = din.reserve(nb * 24)) != hipSuccess || (e = dout.reserve(nb * 17)) != hipSuccess)
-        return hip_fail(e, "hipMalloc (rays)");
-    float* d_o = din.as<float>();
-    float* d_d = d_o + 3 * nb;
-    int32_t* d_id = dout.as<int32_t>();
-    float* d_t = reinterpret_cast<float*>(d_id + nb);
-    float* d_u = d_t + nb;
-    float* d_v = d_u + nb;
-    uint8_t* d_r = reinterpret_cast<uint8_t*>(d_v + nb);
-    if ((e = hipMemcpyAsync(d_o, orig, nb * 12, hipMemcpyHostToDevice, stream_)) != hipSuccess ||
-        (e = hipMemcpyAsync(d_d, dir, nb * 12, hipMemcpyHostToDevice, stream_)) != hipSuccess)
+    const StageArray A[] = {stage_in(orig, 12), stage_in(dir, 12), stage_out(id, 4), stage_out(t, 4),
+                            stage_out(u, 4),    stage_out(v, 4),   stage_out(ret, 1)};
+    RayStage S;
+    hipError_t e = S.upload(A, 7, n, stream_);
+    if (e != hipSuccess)
         return hip_fail(e, "upload (rays)");
-    if ((e = rt_launch_trace_rays(&P, d_o, d_d, (int)n, d_id, d_t, d_u, d_v, d_r, stream_)) != hipSuccess)
-        return hip_fail(e, "trace_rays_kernel launch");
-    if ((e = hipMemcpyAsync(id, d_id, nb * 4, hipMemcpyDeviceToHost, stream_)) != hipSuccess ||
-        (e = hipMemcpyAsync(t, d_t, nb * 4, hipMemcpyDeviceToHost, stream_)) != hipSuccess ||
-        (e = hipMemcpyAsync(u, d_u, nb * 4, hipMemcpyDeviceToHost, stream_)) != hipSuccess ||
-        (e = hipMemcpyAsync(v, d_v, nb * 4, hipMemcpyDeviceToHost, stream_)) != hipSuccess ||
-        (e = hipMemcpyAsync(ret, d_r, nb, hipMemcpyDeviceToHost, stream_)) != hipSuccess)
-        return hip_fail(e, "download (rays)");
-    if ((e = hipStreamSynchronize(stream_)) != hipSuccess)
+    // trace_rays_kernel indexes the [n][3] arrays as 3 * i in 32 bits: a launch takes at most 2^29 rays
+    // (3 * 2^29 < 2^31), and a chunk's pointers are offset here, in 64 bits
+    const int64_t chunk = (int64_t)1 << 29;
+    for (int64_t c0 = 0; c0 < n; c0 += chunk)
+        if ((e = rt_launch_trace_rays(&P, S.at<float>(0) + 3 * c0, S.at<float>(1) + 3 * c0, (int)std::min(chunk, n - c0),
+                                      S.at<int32_t>(2) + c0, S.at<float>(3) + c0, S.at<float>(4) + c0, S.at<float>(5) + c0,
+                                      S.at<uint8_t>(6) + c0, stream_)) != hipSuccess)
+            return hip_fail(e, "trace_rays_kernel launch");
+    if ((e = S.download(stream_)) != hipSuccess)
         return hip_fail(e, "trace_rays_kernel");
     return RT_OK;
 }
@@ -2764,9 +2787,10 @@ int Renderer::trace_rays(const float* orig, const float* dir, int64_t n, int32_t
 // Before a device ray query's launch (rt_trace_rays_device, rt_is_shadowed_device, rt_trace_ray_device;
 // DESIGN.md 13).  For the first two nothing of the scene is validated beyond what a frame's
 // ensure_device_scene refuses: like trace_rays, they read the triangles and the analytic shapes only, no
-// material and no texture.  shaded: the query reads both, and the scene is validated as trace_ray_colors
-// validates it, with its codes.  reads_scene false (the shaded query past its depth limit): the launch reads
-// nothing of the scene, so P and the risk words are left alone.
+// material and no texture.  shaded: the query reads both, and the scene is validated first, with rt_trace_ray's
+// codes and texts (trace_ray_colors comes through here too, with its staging buffer: nptrs 0, no pointer to
+// check).  reads_scene false (the shaded query past its depth limit): the launch reads nothing of the scene, so
+// P and the risk words are left alone.
 int Renderer::begin_ray_query(const char* what, const void* const* ptrs, int nptrs, int n_required, int64_t n,
                               hipStream_t stream, KParams& P, bool shaded, bool reads_scene)
 {
@@ -2796,8 +2820,7 @@ int Renderer::begin_ray_query(const char* what, const void* const* ptrs, int npt
     return prepare_risk(P, stream);
 }
 
-// kind: 0 closest hit, 1 shadow, 2 + rt::SHADE_* the shaded query's instance
-int Renderer::end_ray_query(int kind, int64_t n, hipStream_t stream)
+int Renderer::end_ray_query(QueryKind kind, int64_t n, hipStream_t stream)
 {
     hipError_t e = query_fence_.record(stream, fence_stream_);
     if (e != hipSuccess)
@@ -2818,7 +2841,7 @@ int Renderer::trace_rays_device(const float* d_orig, const float* d_dir, int64_t
     hipError_t e = rt_launch_closest_rays(&P, d_orig, d_dir, (int)n, d_id, d_t, d_u, d_v, d_ret, d_counts, stream);
     if (e != hipSuccess)
         return hip_fail(e, "closest_rays_kernel launch");
-    return end_ray_query(0, n, stream);
+    return end_ray_query(Q_CLOSEST, n, stream);
 }
 
 int Renderer::is_shadowed_device(const float* d_point, const float* d_normal, int64_t n, const float* light,
@@ -2832,75 +2855,88 @@ int Renderer::is_shadowed_device(const float* d_point, const float* d_normal, in
     hipError_t e = rt_launch_shadow_points(&P, d_point, d_normal, (int)n, light ? light : P.light, d_shadowed, stream);
     if (e != hipSuccess)
         return hip_fail(e, "shadow_points_kernel launch");
-    return end_ray_query(1, n, stream);
+    return end_ray_query(Q_SHADOW, n, stream);
+}
+
+// the counters of 'count' kinds from 'first' on (the rt_get_device_* getters)
+static void copy_kinds(const int64_t* from_calls, const int64_t* from_rays, int first, int count, int64_t* calls,
+                       int64_t* rays)
+{
+    std::copy(from_calls + first, from_calls + first + count, calls);
+    std::copy(from_rays + first, from_rays + first + count, rays);
 }
 
 void Renderer::device_ray_queries(int64_t calls[2], int64_t rays[2]) const
 {
-    for (int k = 0; k < 2; k++) {
-        calls[k] = query_calls_[k];
-        rays[k] = query_rays_[k];
-    }
+    copy_kinds(query_calls_, query_rays_, Q_CLOSEST, 2, calls, rays);
 }
 
-// Renderer::trace_ray over n rays in memory of device_, on the caller's stream (rt_trace_ray_device, DESIGN.md
-// 13; kernels.hip shade_rays_kernel): trace_ray_colors' results per ray with no upload, download, allocation
-// or host wait, and nothing shared with band launches (the counts go to the caller's d_counts, not to
-// d_counters_)
-int Renderer::trace_ray_device(const float* d_orig, const float* d_dir, int64_t n, int depth, int64_t first_ray,
-                               float* d_rgba, int32_t* d_src, float* d_t, uint8_t* d_found, uint8_t* d_shadow,
-                               int64_t* d_counts, hipStream_t stream)
+void Renderer::device_shaded_queries(int64_t calls[3], int64_t rays[3]) const
 {
-    return shade_rays_device("trace_ray_device", d_orig, d_dir, n, depth, first_ray, d_rgba, d_src, d_t, d_found, d_shadow,
-                             d_counts, stream);
+    copy_kinds(query_calls_, query_rays_, Q_SHADED_PLAIN, 3, calls, rays);
 }
 
-int Renderer::begin_shaded_query(const char* what, const float* d_orig, const float* d_dir, int64_t n, int depth,
-                                 int64_t first_ray, float* d_rgba, int32_t* d_src, float* d_t, uint8_t* d_found,
-                                 uint8_t* d_shadow, int64_t* d_counts, hipStream_t stream, KParams& P, bool& launch)
+void Renderer::device_shaded_batches(int64_t calls[2], int64_t rays[2]) const
+{
+    copy_kinds(query_calls_, query_rays_, Q_BATCH_ENGINE, 2, calls, rays);
+}
+
+static_assert(Q_SHADOW == Q_CLOSEST + 1 && Q_SHADED_GENERIC == Q_SHADED_PLAIN + SHADE_GENERIC &&
+                  Q_SHADED_REFL == Q_SHADED_PLAIN + SHADE_REFL && Q_BATCH_DELEGATED == Q_BATCH_ENGINE + 1,
+              "the getters report runs of kinds, the shaded ones in SHADE_*'s order");
+
+int Renderer::begin_shaded_query(const char* what, const ShadeRays& q, hipStream_t stream, KParams& P, bool& launch,
+                                 bool staged)
 {
     launch = false;
     // (ray i is keyed as pixel first_ray + i, a 32-bit pixel index; n is bounded first, so no sum overflows)
-    if (depth < 0 || n < 0 || n > (1 << 30) || first_ray < 0 || first_ray > (1ll << 32) - n)
+    if (q.depth < 0 || q.n < 0 || q.n > (1 << 30) || q.first_ray < 0 || q.first_ray > (1ll << 32) - q.n)
         return fail(RT_EINVAL, std::string(what) + ": bad arguments");
-    if (reinterpret_cast<uintptr_t>(d_rgba) & 15u)
+    if (reinterpret_cast<uintptr_t>(q.rgba) & 15u)
         return fail(RT_EINVAL, std::string(what) + ": d_rgba is not 16-byte aligned");
-    const void* const ptrs[] = {d_orig, d_dir, d_rgba, d_src, d_t, d_found, d_shadow, d_counts};
-    const bool past = depth > s_.max_recursion_depth;
-    int rc = begin_ray_query(what, ptrs, 8, 3, n, stream, P, true, !past);
-    if (rc != RT_OK || n == 0)
+    const void* const ptrs[] = {q.orig, q.dir, q.rgba, q.src, q.t, q.found, q.shadow, q.counts};
+    const bool past = q.depth > s_.max_recursion_depth;
+    int rc = begin_ray_query(what, ptrs, staged ? 0 : 8, staged ? 0 : 3, q.n, stream, P, true, !past);
+    if (rc != RT_OK || q.n == 0)
         return rc;
     if (past) {
         // renderer.cpp:1012-1013: Color(0.0f), the record untouched, intersection_found false; no ray is traced
         // and nothing of the scene is read (no parameters, no risk words), so neither the counts nor the fence move
-        hipError_t e =
-            rt_launch_shade_rays_fill((int)n, reinterpret_cast<float4*>(d_rgba), d_src, d_t, d_found, d_shadow, stream);
+        hipError_t e = rt_launch_shade_rays_fill((int)q.n, reinterpret_cast<float4*>(q.rgba), q.src, q.t, q.found,
+                                                 q.shadow, stream);
         return e != hipSuccess ? hip_fail(e, "shade_rays_fill_kernel launch") : RT_OK;
     }
-    P.max_recursion_depth = s_.max_recursion_depth - depth;   // only the difference is read
+    P.max_recursion_depth = s_.max_recursion_depth - q.depth;   // only the difference is read
     launch = true;
     return RT_OK;
 }
 
-int Renderer::shade_rays_device(const char* what, const float* d_orig, const float* d_dir, int64_t n, int depth,
-                                int64_t first_ray, float* d_rgba, int32_t* d_src, float* d_t, uint8_t* d_found,
-                                uint8_t* d_shadow, int64_t* d_counts, hipStream_t stream)
+// Renderer::trace_ray over q's rays in memory of device_, on 'stream' (rt_trace_ray_device and, staged, rt_trace_ray;
+// DESIGN.md 13; kernels.hip shade_rays_kernel): no upload, download, allocation or host wait, and nothing shared
+// with band launches (the counts go to q.counts, not to d_counters_).  The plain instance is the device query's
+// alone: the host call's bytes are the generic and the reflective instance's, whatever the scene.
+int Renderer::shade_rays_device(const char* what, const ShadeRays& q, hipStream_t stream, QueryKind* kind, bool staged)
 {
+    if (kind)
+        *kind = Q_NONE;
     KParams P;
     bool launch;
-    int rc = begin_shaded_query(what, d_orig, d_dir, n, depth, first_ray, d_rgba, d_src, d_t, d_found, d_shadow, d_counts,
-                                stream, P, launch);
+    int rc = begin_shaded_query(what, q, stream, P, launch, staged);
     if (rc != RT_OK || !launch)
         return rc;
     P.counters = nullptr;   // (the handle's counter words belong to the frames)
-    const int inst = P.has_reflection                           ? SHADE_REFL
-                     : P.plain && P.wnodes && knobs_.shade_plain ? SHADE_PLAIN
-                                                                 : SHADE_GENERIC;
-    hipError_t e = rt_launch_shade_rays(&P, inst, d_orig, d_dir, (int)n, (uint32_t)first_ray,
-                                        reinterpret_cast<float4*>(d_rgba), d_src, d_t, d_found, d_shadow, d_counts, stream);
+    const int inst = P.has_reflection                                       ? SHADE_REFL
+                     : P.plain && P.wnodes && knobs_.shade_plain && !staged ? SHADE_PLAIN
+                                                                            : SHADE_GENERIC;
+    hipError_t e = rt_launch_shade_rays(&P, inst, q.orig, q.dir, (int)q.n, (uint32_t)q.first_ray,
+                                        reinterpret_cast<float4*>(q.rgba), q.src, q.t, q.found, q.shadow, q.counts, stream);
     if (e != hipSuccess)
         return hip_fail(e, "shade_rays_kernel launch");
-    return end_ray_query(2 + inst, n, stream);
+    if (staged)
+        return RT_OK;
+    if (kind)
+        *kind = (QueryKind)(Q_SHADED_PLAIN + inst);
+    return end_ray_query((QueryKind)(Q_SHADED_PLAIN + inst), q.n, stream);
 }
 
 // trace_ray_device's arguments and per-ray results, shaded by the frame engine (rt_trace_ray_batch_device, DESIGN.md
@@ -2912,45 +2948,35 @@ int Renderer::shade_rays_device(const char* what, const float* d_orig, const flo
 // first waits for band launches and queries in flight (wait_slots); query_fence_ follows the last resolve.
 // Nothing rt_get_stats or rt_band_counters read is written: last_shadow_ / last_refl_ stay, a band slot has
 // counter words of its own, and d_counters_ is cleared by every frame before it is used.
-int Renderer::trace_ray_batch_device(const float* d_orig, const float* d_dir, int64_t n, int depth, int64_t first_ray,
-                                     float* d_rgba, int32_t* d_src, float* d_t, uint8_t* d_found, uint8_t* d_shadow,
-                                     int64_t* d_counts, hipStream_t stream)
+int Renderer::trace_ray_batch_device(const ShadeRays& q, hipStream_t stream)
 {
     static const char* const what = "trace_ray_batch_device";
     // (KParams::has_reflection and launch_trace's choice, from the host's copies)
     const bool engine = s_.shading_method == RT_SHADING && any_reflection(mats_) && s_.enable_bvh && knobs_.refl_engine;
     if (!engine) {
-        int64_t launches = 0;
-        for (int k = 2; k < 5; k++)
-            launches -= query_calls_[k];
-        int rc = shade_rays_device(what, d_orig, d_dir, n, depth, first_ray, d_rgba, d_src, d_t, d_found, d_shadow,
-                                   d_counts, stream);
-        for (int k = 2; k < 5; k++)
-            launches += query_calls_[k];
-        if (rc == RT_OK && launches > 0) {   // (neither an empty call nor the fill)
-            query_calls_[6]++;
-            query_rays_[6] += n;
+        QueryKind kind;
+        int rc = shade_rays_device(what, q, stream, &kind);
+        if (rc == RT_OK && kind != Q_NONE) {
+            query_calls_[Q_BATCH_DELEGATED]++;
+            query_rays_[Q_BATCH_DELEGATED] += q.n;
         }
         return rc;
     }
     KParams P;
     bool launch;
-    int rc = begin_shaded_query(what, d_orig, d_dir, n, depth, first_ray, d_rgba, d_src, d_t, d_found, d_shadow, d_counts,
-                                stream, P, launch);
+    int rc = begin_shaded_query(what, q, stream, P, launch);
     if (rc != RT_OK || !launch)
         return rc;
-    rc = shade_batches(P, d_orig, d_dir, n, first_ray, d_rgba, d_src, d_t, d_found, d_shadow, d_counts, stream);
+    rc = shade_batches(P, q, stream);
     if (rc != RT_OK) {
         // what was queued before the failure may still run: whatever replaces what it reads waits for it too
         (void)query_fence_.record(stream, fence_stream_);
         return rc;
     }
-    return end_ray_query(5, n, stream);
+    return end_ray_query(Q_BATCH_ENGINE, q.n, stream);
 }
 
-int Renderer::shade_batches(KParams& P, const float* d_orig, const float* d_dir, int64_t n, int64_t first_ray,
-                            float* d_rgba, int32_t* d_src, float* d_t, uint8_t* d_found, uint8_t* d_shadow,
-                            int64_t* d_counts, hipStream_t stream)
+int Renderer::shade_batches(KParams& P, const ShadeRays& q, hipStream_t stream)
 {
     hipError_t e;
     if ((e = d_counters_.reserve(NCOUNTER_WORDS * 8)) != hipSuccess)
@@ -2962,47 +2988,31 @@ int Renderer::shade_batches(KParams& P, const float* d_orig, const float* d_dir,
     P.counters = d_counters_.as<unsigned long long>();
     P.argb = nullptr;
     P.local_rows = 1;   // (refl_level1_begin sizes level 1 for rw x local_rows frames)
-    // Level 1 holds one FrameRec per ray of a batch and n goes up to 2^30.  The offsets are taken here, in 64
-    // bits: the kernels index ints within a batch.
+    // Level 1 holds one FrameRec per ray of a batch and n goes up to 2^30.  The offsets are taken on the host
+    // (ShadeRays::from), in 64 bits: the kernels index ints within a batch.
     const int64_t batch = (int64_t)1 << knobs_.shade_batch_log2;
-    for (int64_t b0 = 0; b0 < n; b0 += batch) {
-        const int nb = (int)std::min(batch, n - b0);
+    for (int64_t b0 = 0; b0 < q.n; b0 += batch) {
+        const ShadeRays b = q.from(b0);
+        const int nb = (int)std::min(batch, b.n);
         P.rw = nb;
-        P.rgba = reinterpret_cast<float4*>(d_rgba) + b0;
-        P.hit_id = d_src ? d_src + b0 : nullptr;
-        P.hit_t = d_t ? d_t + b0 : nullptr;
-        P.shadow = d_shadow ? d_shadow + b0 : nullptr;
+        P.rgba = reinterpret_cast<float4*>(b.rgba);
+        P.hit_id = b.src;
+        P.hit_t = b.t;
+        P.shadow = b.shadow;
         int rc = refl_level1_begin(P, stream);
         if (rc != RT_OK)
             return rc;
         ReflLevel& L1 = refl_[1];
         // (first_ray + n <= 2^32: the key's pixel index fits 32 bits)
-        if ((e = rt_launch_refl_rays_level0(&P, d_orig + 3 * b0, d_dir + 3 * b0, nb, (uint32_t)(first_ray + b0),
-                                            L1.fr.as<FrameRec>(), L1.cnt.as<unsigned int>(), d_found ? d_found + b0 : nullptr,
-                                            stream)) != hipSuccess)
+        if ((e = rt_launch_refl_rays_level0(&P, b.orig, b.dir, nb, (uint32_t)b.first_ray, L1.fr.as<FrameRec>(),
+                                            L1.cnt.as<unsigned int>(), b.found, stream)) != hipSuccess)
             return hip_fail(e, "refl_rays_level0_kernel launch");
         if ((rc = refl_level1_finish(P, stream, "refl_rays_level0_kernel", false)) != RT_OK)
             return rc;
     }
-    if (d_counts && (e = rt_launch_add_ray_counts(P.counters, d_counts, stream)) != hipSuccess)
+    if (q.counts && (e = rt_launch_add_ray_counts(P.counters, q.counts, stream)) != hipSuccess)
         return hip_fail(e, "add_ray_counts_kernel launch");
     return RT_OK;
-}
-
-void Renderer::device_shaded_batches(int64_t calls[2], int64_t rays[2]) const
-{
-    for (int k = 0; k < 2; k++) {
-        calls[k] = query_calls_[5 + k];
-        rays[k] = query_rays_[5 + k];
-    }
-}
-
-void Renderer::device_shaded_queries(int64_t calls[3], int64_t rays[3]) const
-{
-    for (int k = 0; k < 3; k++) {
-        calls[k] = query_calls_[2 + k];
-        rays[k] = query_rays_[2 + k];
-    }
 }
 
 // The frames' wide-BVH query with its status over n host rays (kernels.hip wide_query_kernel): the
@@ -3022,45 +3032,22 @@ int Renderer::wide_query(const float* orig, const float* dir, int64_t n, int kin
         return RT_OK;
     KParams P;
     fill_params(P);
-    DevBuf din, dout;
-    const size_t nb = (size_t)n;
-    hipError_t e;
-    // outputs: o, d (12 B each), status, id, t, u, v (4 B each), shadowed (1 B) per ray
-    constexpr size_t OUT_BYTES = 2 * 12 + 5 * 4 + 1;
-    if ((e = din.reserve(nb * 24)) != hipSuccess || (e = dout.reserve(nb * OUT_BYTES)) != hipSuccess)
-        return hip_fail(e, "hipMalloc (rays)");
-    float* d_o = din.as<float>();
-    float* d_d = d_o + 3 * nb;
-    float* d_oo = dout.as<float>();
-    float* d_do = d_oo + 3 * nb;
-    int32_t* d_st = reinterpret_cast<int32_t*>(d_do + 3 * nb);
-    int32_t* d_id = d_st + nb;
-    float* d_t = reinterpret_cast<float*>(d_id + nb);
-    float* d_u = d_t + nb;
-    float* d_v = d_u + nb;
-    uint8_t* d_sh = reinterpret_cast<uint8_t*>(d_v + nb);
-    if ((size_t)(d_sh + nb - dout.as<uint8_t>()) > dout.bytes)
-        return fail(RT_EINVAL, "wide_query: output layout exceeds its buffer");
     if (wait_slots(stream_) != RT_OK)
         return RT_EHIP;
     if ((rc = prepare_risk(P, stream_)) != RT_OK)
         return rc;
-    if ((e = hipMemcpyAsync(d_o, orig, nb * 12, hipMemcpyHostToDevice, stream_)) != hipSuccess ||
-        (e = hipMemcpyAsync(d_d, dir, nb * 12, hipMemcpyHostToDevice, stream_)) != hipSuccess)
+    const StageArray A[] = {stage_in(orig, 12),  stage_in(dir, 12), stage_out(o_out, 12), stage_out(d_out, 12),
+                            stage_out(status, 4), stage_out(id, 4),  stage_out(t, 4),      stage_out(u, 4),
+                            stage_out(v, 4),      stage_out(shadow, 1)};
+    RayStage S;
+    hipError_t e = S.upload(A, 10, n, stream_);
+    if (e != hipSuccess)
         return hip_fail(e, "upload (rays)");
-    if ((e = rt_launch_wide_query(&P, d_o, d_d, (int)n, kind, d_oo, d_do, d_st, d_id, d_t, d_u, d_v, d_sh, stream_)) !=
-        hipSuccess)
+    if ((e = rt_launch_wide_query(&P, S.at<float>(0), S.at<float>(1), (int)n, kind, S.at<float>(2), S.at<float>(3),
+                                  S.at<int32_t>(4), S.at<int32_t>(5), S.at<float>(6), S.at<float>(7), S.at<float>(8),
+                                  S.at<uint8_t>(9), stream_)) != hipSuccess)
         return hip_fail(e, "wide_query_kernel launch");
-    if ((e = hipMemcpyAsync(o_out, d_oo, nb * 12, hipMemcpyDeviceToHost, stream_)) != hipSuccess ||
-        (e = hipMemcpyAsync(d_out, d_do, nb * 12, hipMemcpyDeviceToHost, stream_)) != hipSuccess ||
-        (e = hipMemcpyAsync(status, d_st, nb * 4, hipMemcpyDeviceToHost, stream_)) != hipSuccess ||
-        (e = hipMemcpyAsync(id, d_id, nb * 4, hipMemcpyDeviceToHost, stream_)) != hipSuccess ||
-        (e = hipMemcpyAsync(t, d_t, nb * 4, hipMemcpyDeviceToHost, stream_)) != hipSuccess ||
-        (e = hipMemcpyAsync(u, d_u, nb * 4, hipMemcpyDeviceToHost, stream_)) != hipSuccess ||
-        (e = hipMemcpyAsync(v, d_v, nb * 4, hipMemcpyDeviceToHost, stream_)) != hipSuccess ||
-        (e = hipMemcpyAsync(shadow, d_sh, nb, hipMemcpyDeviceToHost, stream_)) != hipSuccess)
-        return hip_fail(e, "download (rays)");
-    if ((e = hipStreamSynchronize(stream_)) != hipSuccess)
+    if ((e = S.download(stream_)) != hipSuccess)
         return hip_fail(e, "wide_query_kernel");
     return RT_OK;
 }
@@ -3129,75 +3116,35 @@ int Renderer::risk_words(int src, uint64_t* out, int64_t cap, int64_t* count, in
     return RT_OK;
 }
 
-// Renderer::trace_ray (renderer.cpp:1008-1066) over n host rays at current_recursion_depth
-// 'depth', each with a fresh HitInfo (trace_colors_kernel)
+// Renderer::trace_ray (renderer.cpp:1008-1066) over n host rays at current_recursion_depth 'depth', each with a
+// fresh HitInfo: the arrays staged, then rt_trace_ray_device's own launch over them on stream_ with first_ray 0
+// (shade_rays_device, staged: shade_rays_kernel's generic or reflective instance, or the fill past the depth
+// limit), and rt_get_stats' two counts from the staged counts the kernel adds to (the fill leaves them zero).
 int Renderer::trace_ray_colors(const float* orig, const float* dir, int64_t n, int depth, float* rgba, int32_t* src,
                                float* t, uint8_t* found, uint8_t* shadow)
 {
     if (n < 0 || n > (1 << 30) || depth < 0 ||
         (n > 0 && (!orig || !dir || !rgba || !src || !t || !found || !shadow)))
         return fail(RT_EINVAL, "trace_ray: bad arguments");
-    if (validate() != RT_OK)
-        return fail(RT_EINVAL, "invalid scene: material index out of range or enabled texture map missing");
-    if (check_frame() != RT_OK)
-        return fail(RT_EUNSUPPORTED, "reflective materials with max_recursion_depth > 15");
-    int rc = ensure_device_scene();
-    if (rc != RT_OK)
-        return rc;
-    if (n == 0)
-        return RT_OK;
-    if (depth > s_.max_recursion_depth) {
-        // renderer.cpp:1012-1013: Color(0.0f), the record untouched, intersection_found false
-        for (int64_t i = 0; i < n; i++) {
-            rgba[4 * i] = rgba[4 * i + 1] = rgba[4 * i + 2] = 0.0f;
-            rgba[4 * i + 3] = 1.0f;
-            src[i] = -1;
-            t[i] = -1.0f;
-            found[i] = shadow[i] = 0;
-        }
-        last_shadow_ = last_refl_ = 0;
-        return RT_OK;
-    }
-    KParams P;
-    fill_params(P);
-    P.max_recursion_depth = s_.max_recursion_depth - depth;   // only the difference is read
-    DevBuf din, dout;
-    size_t nb = (size_t)n;
-    hipError_t e;
-    if ((e = din.reserve(nb * 24)) != hipSuccess || (e = dout.reserve(nb * 26)) != hipSuccess ||
-        (e = d_counters_.reserve(NCOUNTER_WORDS * 8)) != hipSuccess)
-        return hip_fail(e, "hipMalloc (rays)");
-    float* d_o = din.as<float>();
-    float* d_d = d_o + 3 * nb;
-    float4* d_rgba = dout.as<float4>();
-    int32_t* d_src = reinterpret_cast<int32_t*>(d_rgba + nb);
-    float* d_t = reinterpret_cast<float*>(d_src + nb);
-    uint8_t* d_found = reinterpret_cast<uint8_t*>(d_t + nb);
-    uint8_t* d_sh = d_found + nb;
-    P.counters = d_counters_.as<unsigned long long>();
-    if (wait_slots(stream_) != RT_OK)   // band launches in flight share the counters' buffer
-        return RT_EHIP;
-    if ((rc = prepare_risk(P, stream_)) != RT_OK)
-        return rc;
-    if ((e = hipMemsetAsync(d_counters_.p, 0, NCOUNTER_WORDS * 8, stream_)) != hipSuccess ||
-        (e = hipMemcpyAsync(d_o, orig, nb * 12, hipMemcpyHostToDevice, stream_)) != hipSuccess ||
-        (e = hipMemcpyAsync(d_d, dir, nb * 12, hipMemcpyHostToDevice, stream_)) != hipSuccess)
+    hipError_t e = hipSetDevice(device_);   // (the staging buffer comes before ensure_device_scene)
+    if (e != hipSuccess)
+        return hip_fail(e, "hipSetDevice");
+    int64_t counts[2] = {0, 0};
+    const StageArray A[] = {stage_in(orig, 12), stage_in(dir, 12),  stage_out(rgba, 16),  stage_out(src, 4),
+                            stage_out(t, 4),    stage_out(found, 1), stage_out(shadow, 1),
+                            {counts, sizeof(counts), STAGE_UP | STAGE_DOWN | STAGE_ONCE}};
+    RayStage S;   // (empty for n == 0: null arrays, which the refusals below do not read)
+    if (n > 0 && (e = S.upload(A, 8, n, stream_)) != hipSuccess)
         return hip_fail(e, "upload (rays)");
-    if ((e = rt_launch_trace_colors(&P, P.has_reflection, d_o, d_d, (int)n, d_rgba, d_src, d_t, d_found, d_sh,
-                                    stream_)) != hipSuccess)
-        return hip_fail(e, "trace_colors_kernel launch");
-    unsigned long long cnt[NCOUNTERS] = {};
-    if ((e = hipMemcpyAsync(rgba, d_rgba, nb * 16, hipMemcpyDeviceToHost, stream_)) != hipSuccess ||
-        (e = hipMemcpyAsync(src, d_src, nb * 4, hipMemcpyDeviceToHost, stream_)) != hipSuccess ||
-        (e = hipMemcpyAsync(t, d_t, nb * 4, hipMemcpyDeviceToHost, stream_)) != hipSuccess ||
-        (e = hipMemcpyAsync(found, d_found, nb, hipMemcpyDeviceToHost, stream_)) != hipSuccess ||
-        (e = hipMemcpyAsync(shadow, d_sh, nb, hipMemcpyDeviceToHost, stream_)) != hipSuccess ||
-        (e = hipMemcpyAsync(cnt, d_counters_.p, sizeof(cnt), hipMemcpyDeviceToHost, stream_)) != hipSuccess)
-        return hip_fail(e, "download (rays)");
-    if ((e = hipStreamSynchronize(stream_)) != hipSuccess)
-        return hip_fail(e, "trace_colors_kernel");
-    last_shadow_ = (int64_t)cnt[0];
-    last_refl_ = (int64_t)cnt[1];
+    const ShadeRays q{S.at<float>(0),   S.at<float>(1),   n, depth, 0, S.at<float>(2), S.at<int32_t>(3), S.at<float>(4),
+                      S.at<uint8_t>(5), S.at<uint8_t>(6), S.at<int64_t>(7)};
+    int rc = shade_rays_device("trace_ray", q, stream_, nullptr, true);
+    if (rc != RT_OK || n == 0)
+        return rc;
+    if ((e = S.download(stream_)) != hipSuccess)
+        return hip_fail(e, "shade_rays_kernel");
+    last_shadow_ = counts[0];
+    last_refl_ = counts[1];
     return RT_OK;
 }
 

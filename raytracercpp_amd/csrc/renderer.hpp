@@ -171,6 +171,41 @@ struct Knobs {
     static Knobs from_env();
 };
 
+// The shaded ray query's arguments as one value (rt_trace_ray_device's, in its order): n rays in memory of the
+// renderer's device at current_recursion_depth 'depth', ray i keyed as pixel first_ray + i.  Every output but rgba
+// may be null; counts (null or int64[2]) += the call's shadow and reflection rays.
+struct ShadeRays {
+    const float *orig, *dir;   // [n][3]
+    int64_t n;
+    int depth;
+    int64_t first_ray;
+    float* rgba;               // [n][4]
+    int32_t* src;
+    float* t;
+    uint8_t *found, *shadow;
+    int64_t* counts;
+    // the rays from b0 on (in 64 bits: the kernels index ints within a launch); a null output stays null
+    ShadeRays from(int64_t b0) const
+    {
+        return {orig + 3 * b0, dir + 3 * b0, n - b0, depth, first_ray + b0, rgba + 4 * b0, src ? src + b0 : nullptr,
+                t ? t + b0 : nullptr, found ? found + b0 : nullptr, shadow ? shadow + b0 : nullptr, counts};
+    }
+};
+
+// What the device ray queries count (query_calls_ / query_rays_, end_ray_query).  The three shaded kinds keep the
+// order of rt::SHADE_* (launch.hpp), the order rt_get_device_shaded_queries reports.
+enum QueryKind {
+    Q_CLOSEST,           // trace_rays_device
+    Q_SHADOW,            // is_shadowed_device
+    Q_SHADED_PLAIN,      // trace_ray_device by instance of shade_rays_kernel
+    Q_SHADED_GENERIC,
+    Q_SHADED_REFL,
+    Q_BATCH_ENGINE,      // trace_ray_batch_device through the frame engine
+    Q_BATCH_DELEGATED,   // ... handed to trace_ray_device's code (counted there too)
+    Q_KINDS,
+    Q_NONE = -1,         // nothing was launched for the scene's rays: an empty call, or the fill past the depth limit
+};
+
 class Renderer {
 public:
     explicit Renderer(int device);
@@ -288,20 +323,15 @@ public:
                            uint8_t* d_shadowed, hipStream_t stream);
     // launches of the two kernels since rt_create and the rays given to them (rt_get_device_ray_queries)
     void device_ray_queries(int64_t calls[2], int64_t rays[2]) const;
-    // Renderer::trace_ray (shaded) over n rays in memory of device_ at current_recursion_depth 'depth', ray i keyed
-    // as pixel first_ray + i, on the caller's stream (rt_trace_ray_device); every output but d_rgba may be null
-    int trace_ray_device(const float* d_orig, const float* d_dir, int64_t n, int depth, int64_t first_ray, float* d_rgba,
-                         int32_t* d_src, float* d_t, uint8_t* d_found, uint8_t* d_shadow, int64_t* d_counts,
-                         hipStream_t stream);
+    // Renderer::trace_ray (shaded) over q's rays in memory of device_, on the caller's stream (rt_trace_ray_device)
+    int trace_ray_device(const ShadeRays& q, hipStream_t stream) { return shade_rays_device("trace_ray_device", q, stream); }
     // its launches and rays since rt_create by instance: plain, generic, reflective (rt_get_device_shaded_queries)
     void device_shaded_queries(int64_t calls[3], int64_t rays[3]) const;
     // trace_ray_device's arguments and per-ray results through the frame engine (rt_trace_ray_batch_device, DESIGN.md
     // 13): a scene with a reflective material, the BVH and the engine on is shaded level by level in batches of
     // 2^RT_SHADE_BATCH_LOG2 rays on the caller's stream; the host waits for the engine's counts, the call may
     // allocate, and the stream first waits for band launches and queries in flight.  Any other scene: trace_ray_device.
-    int trace_ray_batch_device(const float* d_orig, const float* d_dir, int64_t n, int depth, int64_t first_ray,
-                               float* d_rgba, int32_t* d_src, float* d_t, uint8_t* d_found, uint8_t* d_shadow,
-                               int64_t* d_counts, hipStream_t stream);
+    int trace_ray_batch_device(const ShadeRays& q, hipStream_t stream);
     // its calls and rays since rt_create: [0] through the engine, [1] handed to trace_ray_device
     // (rt_get_device_shaded_batches)
     void device_shaded_batches(int64_t calls[2], int64_t rays[2]) const;
@@ -355,30 +385,27 @@ private:
     // The device ray queries (trace_rays_device, is_shadowed_device, trace_ray_device).  query_fence_ follows the
     // last launch on any stream: fence_stream_ runs in order, so the last record() comes after every earlier one.
     Fence query_fence_;
-    // closest hit, shadow, shaded: plain, generic, reflective, shaded batches: through the engine, delegated
-    int64_t query_calls_[7] = {}, query_rays_[7] = {};
+    int64_t query_calls_[Q_KINDS] = {}, query_rays_[Q_KINDS] = {};
     // before a query launch on 'stream': the count and the pointers (n_required of them must not be null when
-    // n > 0; each must be memory of device_), the scene as a frame brings it up to date (shaded: validated as
-    // trace_ray_colors validates it first), P with its risk words (reads_scene false: neither; the launch reads
-    // nothing of the scene)
+    // n > 0; each must be memory of device_; nptrs 0: the renderer's own staging buffer, nothing to check), the
+    // scene as a frame brings it up to date (shaded: validated first, with rt_trace_ray's codes and texts), P with
+    // its risk words (reads_scene false: neither; the launch reads nothing of the scene)
     int begin_ray_query(const char* what, const void* const* ptrs, int nptrs, int n_required, int64_t n,
                         hipStream_t stream, KParams& P, bool shaded = false, bool reads_scene = true);
-    // after it: the fence and the counters (kind 0 closest hit, 1 shadow, 2 + the shaded query's instance, 5 a
-    // shaded batch through the engine)
-    int end_ray_query(int kind, int64_t n, hipStream_t stream);
-    // The start the two shaded device queries share ('what': the caller's name in the error texts): the argument
-    // checks, begin_ray_query, and past the depth limit the fill.  launch: rays are left for the caller to shade
-    int begin_shaded_query(const char* what, const float* d_orig, const float* d_dir, int64_t n, int depth,
-                           int64_t first_ray, float* d_rgba, int32_t* d_src, float* d_t, uint8_t* d_found,
-                           uint8_t* d_shadow, int64_t* d_counts, hipStream_t stream, KParams& P, bool& launch);
-    // trace_ray_device under the caller's name
-    int shade_rays_device(const char* what, const float* d_orig, const float* d_dir, int64_t n, int depth,
-                          int64_t first_ray, float* d_rgba, int32_t* d_src, float* d_t, uint8_t* d_found,
-                          uint8_t* d_shadow, int64_t* d_counts, hipStream_t stream);
+    // after it: the fence and the counters
+    int end_ray_query(QueryKind kind, int64_t n, hipStream_t stream);
+    // The start the shaded queries share ('what': the caller's name in the error texts): the argument checks,
+    // begin_ray_query, and past the depth limit the fill.  launch: rays are left for the caller to shade.
+    // staged: q is the host call's staging buffer (trace_ray_colors, which has checked its own arrays)
+    int begin_shaded_query(const char* what, const ShadeRays& q, hipStream_t stream, KParams& P, bool& launch,
+                           bool staged = false);
+    // trace_ray_device under the caller's name; *kind: what it counted (Q_SHADED_*, or Q_NONE).  staged: the host
+    // call's launch, which waits for the stream itself and is no device query -- never the plain instance, no
+    // fence, nothing counted
+    int shade_rays_device(const char* what, const ShadeRays& q, hipStream_t stream, QueryKind* kind = nullptr,
+                          bool staged = false);
     // trace_ray_batch_device's engine passes over the batches (the fence follows, whatever they return)
-    int shade_batches(KParams& P, const float* d_orig, const float* d_dir, int64_t n, int64_t first_ray, float* d_rgba,
-                      int32_t* d_src, float* d_t, uint8_t* d_found, uint8_t* d_shadow, int64_t* d_counts,
-                      hipStream_t stream);
+    int shade_batches(KParams& P, const ShadeRays& q, hipStream_t stream);
 
     Knobs knobs_;
     int device_;

@@ -6,7 +6,8 @@ frames by tests/test_trace_ray.py) writes for that ray in the same renderer stat
 bit, the counts rt_get_stats reports after the host call, and the colour bit for bit where the generic or the
 reflective instance runs.  Where the plain instance runs (a scene the frames render with their plain pixel, over
 a resident wide BVH) the colour is held to the oracle's within RGBA_TOL and, for camera rays, to the float RGBA
-of a frame of the same renderer bit for bit."""
+of a frame of the same renderer bit for bit.  rt_trace_ray stages its arrays and runs the generic or the reflective
+instance itself, so every instance is also held to the oracle directly, on every 10th ray."""
 import ctypes as C
 import dataclasses
 
@@ -130,6 +131,10 @@ def test_equals_trace_ray(R, name):
     R.load_scene(c.scene, c.settings)
     o, d = random_rays(c)
     od, dd = gpu(o), gpu(d)
+    # every 10th ray, from both halves of the set, for the oracle (a call of its own: ray j draws pixel j's stream)
+    o10, d10 = np.ascontiguousarray(o[::10]), np.ascontiguousarray(d[::10])
+    assert len(o10) == 2000
+    orc, oracle = Oracle(c.scene, c.settings), {}   # (its answers by depth, computed once each)
     for depth in (0, 1, c.settings.max_recursion_depth + 1):
         ref, cnt = ref_of(R, o, d, depth)
         calls0, rays0 = R.device_shaded_queries()
@@ -153,6 +158,17 @@ def test_equals_trace_ray(R, name):
             assert (inst == [REFL]) == reflective(c)
             if name in ("textured", "diffuse_map_skysphere", "shading_3"):
                 assert inst == [GENERIC]
+        # rt_trace_ray runs the same kernel in the generic and the reflective instance: every instance is also
+        # held to the oracle itself, at depths 0 and 1
+        if depth <= 1 and depth not in oracle:
+            e = oracle[depth] = orc.trace_ray(o10, d10, depth)
+            counts10 = zeros2()
+            got10 = host(R.trace_ray_device(gpu(o10), gpu(d10), depth, counts=counts10))
+            same(got10, e, f"{name}, depth {depth}, against the oracle", rgba=False)
+            err = float(np.abs(got10[0] - e[0]).max())
+            print(f"{name}, depth {depth}: max |RGBA - oracle| {err:.3g} over {len(o10)} rays, counts {counts10.tolist()}")
+            assert err <= RGBA_TOL, f"{name}, depth {depth}"
+            assert tuple(counts10.tolist()) == (e[5]["shadow_rays"], e[5]["reflection_rays"]), f"{name}, depth {depth}"
 
 
 # ---- 2. the plain instance --------------------------------------------------------------------------------
@@ -194,6 +210,9 @@ def test_plain_instance(make_renderer, plain_ref, state):
           f"bits; {nframe} of {ncam} camera rays differ from the frame's float RGBA")
     assert np.array_equal(got[1], e[1]) and np.array_equal(bits(got[2]), bits(e[2]))
     assert err <= RGBA_TOL
+    if state == "RT_SHADE_PLAIN=0":
+        # the generic instance is the one rt_trace_ray runs on this scene: its expressions, so its bits
+        assert nbits == 0, f"{state}: the colours of {nbits} rays differ from rt_trace_ray's in their bits"
     assert nframe == 0, f"{state}: the colours of {nframe} camera rays differ from the frame's"
     assert np.array_equal(np.where(got[3][:ncam] == 1, got[1][:ncam], -1), fr["hit_id"])
     assert np.array_equal(bits(got[2][:ncam]), bits(fr["hit_t"])) and np.array_equal(got[4][:ncam], fr["shadow"])
@@ -283,6 +302,30 @@ def test_empty_call_launches_nothing(R, rough):
     assert _lib.lib().rt_trace_ray_device(R._h, None, None, 0, 0, 0, None, None, None, None, None, None, None) == 0
     assert R.device_shaded_queries() == before
     assert R.trace_ray_device(e, e.clone())["rgba"].shape == (0, 4)
+
+
+@pytest.mark.parametrize("name", ["rough", "textured"])
+def test_host_queries_leave_device_counters_alone(R, name):
+    """rt_trace_ray runs the device query's kernel over a staged copy of its arrays, one block and a lane here; it
+    is no device query, and neither are rt_trace_rays and rt_wide_query."""
+    c = case(name)
+    R.load_scene(c.scene, c.settings)
+    o, d = random_rays(c, BLOCK + 1)
+
+    def counters():
+        return R.device_ray_queries(), R.device_shaded_queries(), R.device_shaded_batches()
+
+    before = counters()
+    rgba = R.trace_ray(o, d, 0)[0]
+    assert rgba.shape == (BLOCK + 1, 4) and counters() == before, "trace_ray at depth 0"
+    past = R.trace_ray(o, d, c.settings.max_recursion_depth + 1)
+    st = R.stats()
+    assert (st["shadow_rays"], st["reflection_rays"]) == (0, 0)
+    assert np.all(past[0] == np.array([0, 0, 0, 1], np.float32)) and np.all(past[1] == -1)
+    assert np.all(past[2] == -1.0) and not past[3].any() and not past[4].any()
+    assert counters() == before, "trace_ray past the depth limit"
+    assert len(R.trace_rays(o, d)[0]) == BLOCK + 1 and counters() == before, "trace_rays"
+    assert len(R.wide_query(o, d, kind=0)["status"]) == BLOCK + 1 and counters() == before, "wide_query"
 
 
 # ---- 4. first_ray -----------------------------------------------------------------------------------------
@@ -460,7 +503,7 @@ def test_band_launch_beside_a_query(make_renderer, name):
     o, d = random_rays(c, n, seed=4)
     od, dd = gpu(o), gpu(d)
     ref, cnt = ref_of(r, o[:N], d[:N])
-    r.render_bands_device(8, 0, 1, alone.data_ptr(), 0)   # (rt_trace_ray cleared the shared counters: again)
+    r.render_bands_device(8, 0, 1, alone.data_ptr(), 0)   # (a launch after the host call counts what the one before it did)
     torch.cuda.synchronize()
     assert r.band_counters() == want_counters
     s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
