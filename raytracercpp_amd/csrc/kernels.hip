@@ -45,6 +45,23 @@ __device__ __forceinline__ void w_step_hook(uint32_t cur, int leaf)
     }
 }
 #define W_STEP_HOOK(cur, leaf) w_step_hook(cur, leaf)
+// g_wnob: [0] the wave node steps whose active lanes all skip case (b) (nob), [1] the lanes in them, [2] every
+// wave node step, [3] the lanes in them (DESIGN.md 5.10's S = [0] / [2])
+__device__ unsigned long long g_wnob[4];
+__device__ __forceinline__ void w_nob_hook(bool nob)
+{
+    const uint64_t act = __ballot(1);
+    const bool all = __ballot(!nob) == 0ull;
+    if ((int)__lane_id() == __ffsll((unsigned long long)act) - 1) {
+        if (all) {
+            atomicAdd(&g_wnob[0], 1ull);
+            atomicAdd(&g_wnob[1], (unsigned long long)__popcll(act));
+        }
+        atomicAdd(&g_wnob[2], 1ull);
+        atomicAdd(&g_wnob[3], (unsigned long long)__popcll(act));
+    }
+}
+#define W_NOB_HOOK(nob) w_nob_hook(nob)
 #endif
 #include "kparams.hpp"
 #include "rt_math.hpp"
@@ -965,8 +982,11 @@ __device__ __forceinline__ float wide_margin(const KParams& P, v3 o)
 
 // wbvh_closest on the lane's LDS stack (Stk over lv), and again through wide_closest_deep when that
 // overflows.  count: the query kind's first word for count_wave_steps (RT_COUNT builds; < 0: the query
-// is not counted)
-template <class Stk, int G>
+// is not counted).  NOBF (the frame kernels' camera and shadow rays, W_NOB_FAST): the general instance loads the
+// risk words only on the lanes that can read them (LAZY), and (W_NOB_FAST 2) a wave none of whose active lanes has
+// !nob (a lane group: no lane of the wave) runs the instance without case (b); the test is wave-uniform, so a wave
+// runs one instance per query.  Every other caller's query is the general instance as it was
+template <class Stk, int G, bool NOBF = false>
 __device__ __forceinline__ int wide_run(const KParams& P, v3 o, v3 d, uint2* lv, WHit& w, float hi, bool ties, float QS,
                                         const uint64_t* rk, int rsel, float rsub, uint32_t max_steps, bool nob, int count,
                                         const uint32_t* start = nullptr)
@@ -979,8 +999,15 @@ __device__ __forceinline__ int wide_run(const KParams& P, v3 o, v3 d, uint2* lv,
 #else
     uint32_t* wk = nullptr;
 #endif
-    int st = wbvh_closest<Stk, G>(P.wnodes, P.wtris, o, d, m, stk, w, wk, hi, ties, QS, rk, rsel, rsub, max_steps,
-                                  (WNoFeed*)nullptr, nob, start);
+    int st;
+    // (the general instance first: in the other order the compiler reloaded a spilled value once per child
+    // inside the general instance's node step)
+    if (!(NOBF && W_NOB_FAST >= 2) || __ballot(!nob) != 0ull)
+        st = wbvh_closest<Stk, G, WNoFeed, false, NOBF>(P.wnodes, P.wtris, o, d, m, stk, w, wk, hi, ties, QS, rk, rsel, rsub,
+                                                        max_steps, (WNoFeed*)nullptr, nob, start);
+    else
+        st = wbvh_closest<Stk, G, WNoFeed, true>(P.wnodes, P.wtris, o, d, m, stk, w, wk, hi, ties, QS, rk, rsel, rsub,
+                                                 max_steps, (WNoFeed*)nullptr, true, start);
 #if RT_COUNT
     if (wk) {
         count_wave_steps(P, count, wk[3]);
@@ -1041,7 +1068,7 @@ __device__ __forceinline__ bool wide_closest(const KParams& P, v3 o, v3 d, THit&
                 const uint4 e = ldg(P.tile_start + bidx);
                 s[0] = e.x; s[1] = e.y; s[2] = e.z; s[3] = e.w;
             }
-            st = wide_run<Stk, G>(P, o, d, lv, w, INFINITY, true, W_QS_CLOSEST, rk, 0, 0.0f, RT_COUNT ? 0u : max_steps, nob, 22, s);
+            st = wide_run<Stk, G, true>(P, o, d, lv, w, INFINITY, true, W_QS_CLOSEST, rk, 0, 0.0f, RT_COUNT ? 0u : max_steps, nob, 22, s);
         } else
             st = wide_run<Stk, G>(P, o, d, lv, w, INFINITY, true, W_QS_CLOSEST, rk, 0, 0.0f, RT_COUNT ? 0u : max_steps, nob, 22);
     }
@@ -1089,7 +1116,8 @@ __device__ __forceinline__ bool wide_closest(const KParams& P, v3 o, v3 d, THit&
 // Returns true when decided (shadowed in *sh); false: take the octree segment query.
 // light: the ray is one of the frame's shadow rays towards P.light that may read its risk keys
 // (KParams::wrisk; hi >= |light - o|)
-template <int G = 1, int CAP = W_STACK>
+// NOBF: wide_run's (the plain frame pixel's shadow rays)
+template <int G = 1, int CAP = W_STACK, bool NOBF = false>
 __device__ __forceinline__ bool wide_shadow(const KParams& P, v3 o, v3 d, float hi, v3 p, v3 lp, uint2* lv, bool* sh,
                                             bool light)
 {
@@ -1101,7 +1129,7 @@ __device__ __forceinline__ bool wide_shadow(const KParams& P, v3 o, v3 d, float 
     // the origin face away from it; ocone.hpp, built for W_QS_CLOSEST >= W_QS_SHADOW, so for a superset)
     static_assert(W_QS_SHADOW <= W_QS_CLOSEST, "the origin cones hold the at-risk triangles for the larger split");
     const bool nob = ocone_skip(P.ocone, o, d, W_QS_SHADOW) || (light && P.risk_cap && risk_cap_skip(P.risk_cap[1], P.cap_dir[1], d, W_QS_SHADOW));
-    const int st = wide_run<Stk, G>(P, o, d, lv, w, hi, false, W_QS_SHADOW, rk, 1, rsub, 0u, nob, 25);
+    const int st = wide_run<Stk, G, NOBF>(P, o, d, lv, w, hi, false, W_QS_SHADOW, rk, 1, rsub, 0u, nob, 25);
     if (st == W_MISS) {
         *sh = false;
         return true;
@@ -1232,7 +1260,7 @@ __device__ bool is_shadowed(const KParams& P, v3 p, v3 n, v3 lp, uint2* lv)
         // (seg_scale > 0: no analytic shapes, so shapes_shadow below has nothing to add)
         bool sh;
         if (!OCT && P.wnodes && P.nnodes > 0 && !nan &&
-            wide_shadow<G, PLAIN ? W_STACK_PLAIN : W_STACK>(P, o, d, hi, p, lp, lv, &sh, light))
+            wide_shadow<G, PLAIN ? W_STACK_PLAIN : W_STACK, PLAIN>(P, o, d, hi, p, lp, lv, &sh, light))
             return sh;
         const OctQ q = octree_query<CALL>(P, o, d, -m, hi, P.seg_oct != 0, lv);
         h = q.h;
@@ -1569,8 +1597,10 @@ struct PixelOut {
 
 // Renderer::trace_ray (renderer.cpp:1008-1066) for one primary ray, with the
 // compute_reflection recursion (when REFL) unrolled onto an explicit stack.
+// (Inlined into every caller, as it always was: with the plain pixel's second query instance, wide_run's NOBF, the
+// compiler would otherwise keep the plain instance out of line and spill around the call.)
 template <bool REFL, bool PLAIN = false, int G = 1, bool OCT = false>
-__device__ PixelOut trace_pixel(const KParams& P, v3 cam, v3 rd0, uint2* lv, uint32_t pixel_key, unsigned& nshadow,
+__device__ __forceinline__ PixelOut trace_pixel(const KParams& P, v3 cam, v3 rd0, uint2* lv, uint32_t pixel_key, unsigned& nshadow,
                                 unsigned& nrefl, int bidx = -1)
 {
     PixelOut po;
@@ -4640,5 +4670,12 @@ extern "C" __attribute__((visibility("default"))) int rt_diag_wave_steps(unsigne
     unsigned long long z[8] = {};
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wsteps), sizeof(z)) != hipSuccess) return -1;
     return hipMemcpyToSymbol(HIP_SYMBOL(g_wsteps), z, sizeof(z)) == hipSuccess ? 0 : -1;
+}
+// likewise g_wnob (4 words)
+extern "C" __attribute__((visibility("default"))) int rt_diag_nob_steps(unsigned long long* out)
+{
+    unsigned long long z[4] = {};
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wnob), sizeof(z)) != hipSuccess) return -1;
+    return hipMemcpyToSymbol(HIP_SYMBOL(g_wnob), z, sizeof(z)) == hipSuccess ? 0 : -1;
 }
 #endif

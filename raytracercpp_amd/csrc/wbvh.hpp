@@ -81,6 +81,19 @@ constexpr int W_WIDTH = 4;    // children per node
 #ifndef W_STEP_HOOK
 #define W_STEP_HOOK(cur, leaf)   // diagnostic builds (kernels.hip): per-step wave statistics
 #endif
+#ifndef W_NOB_HOOK
+#define W_NOB_HOOK(nob)   // diagnostic builds (kernels.hip): the node steps whose lanes all skip case (b)
+#endif
+
+// Case (b) of wbvh_closest for rays that skip it (nob):
+//   0: the risk words are loaded for every ray with risk keys, and every query runs the general instance;
+//   1: in the frame kernels' queries (wbvh_closest<.., LAZY = true>, kernels.hip wide_run's NOBF) the risk words
+//      are loaded only by the lanes that can read them (risk keys and !nob);
+//   2: 1, and a wave of those queries whose active lanes all have nob runs the instance compiled without
+//      case (b) (wbvh_closest<.., NOB = true>).
+#ifndef W_NOB_FAST
+#define W_NOB_FAST 2
+#endif
 
 // cone threshold step: c in 0..254 encodes c * 224 / 254 >= |N| (|N| <= 127 sqrt 3 < 220), so 255
 // can never pass.  W_CONE_EPS: the triangles' minimum cos(normal, d) the build guarantees
@@ -1490,7 +1503,13 @@ RT_HD T wg_read(T x, int i)
 //       without risk keys).
 // Robustly back-facing children (the cone) report nothing and are skipped as before.
 // nob: no triangle with q < QS can report a hit for this ray (ocone.hpp ocone_skip, the origin cones),
-// so case (b) is skipped (with or without risk words).
+// so case (b) is skipped (with or without risk words).  Such a ray reads no risk word: LAZY (compile time, with
+// W_NOB_FAST; the frame kernels' queries, kernels.hip wide_run) loads them only on the lanes with risk keys and !nob
+// (the others take zeros, which no path of theirs reads); without LAZY every lane with risk keys loads them.
+// NOB (compile time): the caller promises that nob is true on every lane.  The instance is the same text
+// without the risk words, rkj / kbl, both case (b) branches, their ext2 word, dchild and wq_h0: with nob true
+// the general instance enters neither branch and reads rw[] nowhere else, so the two take the same decisions,
+// keys, order and answers, and count the same work, visit for visit (tests/c/nob_instance_check.cpp).
 // risk (optional): the risk words of the ray's kind rsel (wrisk_pack / wbvh_risk_host / kernels.hip
 // wide_risk_kernel): a child whose key is INFINITY holds no triangle that can report a hit in case (b)
 // for this ray; its (b) triangles lie in octree leaves inside its at-risk box (so the line must cross
@@ -1521,7 +1540,7 @@ struct WNoFeed {
     RT_HD bool fetch(bool, v3&, v3&, float&, bool&) { return false; }
 };
 
-template <class Stack, int G = 1, class Feed = WNoFeed>
+template <class Stack, int G = 1, class Feed = WNoFeed, bool NOB = false, bool LAZY = false>
 RT_HD int wbvh_closest(const WNode* nodes, const GTri* tris, v3 o, v3 d, float m, Stack& stk, WHit& h,
                        uint32_t* work = nullptr, float hi = INFINITY, bool ties = true, float QS = 0x1p-8f,
                        const uint64_t* risk = nullptr, int rsel = 0, float rsub = 0.0f, uint32_t max_steps = 0,
@@ -1537,6 +1556,7 @@ RT_HD int wbvh_closest(const WNode* nodes, const GTri* tris, v3 o, v3 d, float m
     // call's: the same state, reset per query, the same steps.  Returns W_MISS once the feed is drained.
     constexpr bool FEED = Feed::on;
     static_assert(!FEED || G == 1, "lane refill: one lane per query");
+    static_assert(!FEED || !NOB, "lane refill: nob comes with each ray (Feed::fetch)");
     // the stack index of entry i (a ring in a lane group)
     auto slot = [](int i) { return G > 1 ? (i & (Stack::CAP - 1)) : i; };
     h.t = INFINITY;
@@ -1647,6 +1667,7 @@ RT_HD int wbvh_closest(const WNode* nodes, const GTri* tris, v3 o, v3 d, float m
         if (!(cur & W_LEAF)) {
             nn++;
             W_STEP_HOOK(cur, 0);
+            W_NOB_HOOK(NOB || nob);
             const uint4* p = reinterpret_cast<const uint4*>(nodes + cur);
             constexpr int NR = WN_ROWS;
             uint4 Rw[NR];
@@ -1690,9 +1711,12 @@ RT_HD int wbvh_closest(const WNode* nodes, const GTri* tris, v3 o, v3 d, float m
                 const float fz = fmaxf(fabsf(Dz), fabsf(__builtin_fmaf(255.0f, stz, Dz)));
                 Dn = fast_sqrt(fx * fx + fy * fy + fz * fz) * (1.0f + 0x1p-16f) + m;
             }
-            // the children's risk words for this ray's kind (wrisk_pack): key and at-risk box
-            uint32_t rw[2 * W_WIDTH];
-            if (risk) {
+            // the children's risk words for this ray's kind (wrisk_pack): key and at-risk box, for the lanes
+            // whose case (b) can read them (a wave with no such lane skips the loads and their addresses)
+            [[maybe_unused]] uint32_t rw[2 * W_WIDTH];
+            if constexpr (NOB)
+                ;   // (no case (b): nothing reads them)
+            else if (LAZY && W_NOB_FAST ? risk && !nob : risk != nullptr) {
                 const uint4* rp = reinterpret_cast<const uint4*>(risk + (2 * (size_t)cur + rsel) * W_WIDTH);
                 const uint4 r0 = ldg(rp), r1 = ldg(rp + 1);
                 rw[0] = r0.x; rw[1] = r0.y; rw[2] = r0.z; rw[3] = r0.w;
@@ -1731,7 +1755,7 @@ RT_HD int wbvh_closest(const WNode* nodes, const GTri* tris, v3 o, v3 d, float m
                     // D for case (b): o to the farthest corner of child j's box (it holds the child's
                     // vertices; Dn's frame can be several times larger, and near the origin (b) is priced
                     // by D sin(theta)).  Case (a) keeps the node frame's Dn (sound either way)
-                    auto dchild = [&]() -> float {
+                    [[maybe_unused]] auto dchild = [&]() -> float {
                         const float fx = fmaxf(fabsf(__builtin_fmaf(qnx, stx, Dx)), fabsf(__builtin_fmaf(qfx, stx, Dx)));
                         const float fy = fmaxf(fabsf(__builtin_fmaf(qny, sty, Dy)), fabsf(__builtin_fmaf(qfy, sty, Dy)));
                         const float fz = fmaxf(fabsf(__builtin_fmaf(qnz, stz, Dz)), fabsf(__builtin_fmaf(qfz, stz, Dz)));
@@ -1800,49 +1824,51 @@ RT_HD int wbvh_closest(const WNode* nodes, const GTri* tris, v3 o, v3 d, float m
                     // (the child box widened by rho, any t), and the origin must lie within H0
                     // (wq_h0) of a triangle's plane, so within H0 + D sin(theta)
                     // of the child's slab (D = dchild() >= |o - a|)
-                    const float rkj = bitsf(rw[2 * j + 1] & 0xFFFF0000u);   // wrisk_key
-                    const float kbl = (rkj - rsub) * iqd;
-                    if (!risk && !nob && qlb < QS) {
-                        // no risk words (reflection rays, rt_trace_ray):
-                        // the child box widened by m + rho (any t) and the origin within H0 + D sin(theta) of
-                        // the slab; keyed 0 (no risk key bounds the reports' t)
-                        float umin, umax;
-                        const uint32_t e2 = wd(WN_EXT2 + j);
-                        box(m + wq_len(e2 & 0xffu), umin, umax);
-                        bool okb = !(umin > __builtin_fmaf(fabsf(umax), SL, umax));
-                        if (okb) {
-                            const float s2 = wq_val_nz((e >> 8) & 0xffu, WQ_UNIT);
-                            const float Dc = dchild();
-                            const float H0 = wq_h0(QS, L, Dc, smin, s2);
-                            const float w = NLH * (H0 + __builtin_fmaf(Dc, sth, m)) * (1.0f + 0x1p-16f) + 384.0f * m;
-                            okb = !(-b < C0 - w || -b > C1 + w);
+                    if constexpr (!NOB) {
+                        const float rkj = bitsf(rw[2 * j + 1] & 0xFFFF0000u);   // wrisk_key
+                        const float kbl = (rkj - rsub) * iqd;
+                        if (!risk && !nob && qlb < QS) {
+                            // no risk words (reflection rays, rt_trace_ray):
+                            // the child box widened by m + rho (any t) and the origin within H0 + D sin(theta) of
+                            // the slab; keyed 0 (no risk key bounds the reports' t)
+                            float umin, umax;
+                            const uint32_t e2 = wd(WN_EXT2 + j);
+                            box(m + wq_len(e2 & 0xffu), umin, umax);
+                            bool okb = !(umin > __builtin_fmaf(fabsf(umax), SL, umax));
+                            if (okb) {
+                                const float s2 = wq_val_nz((e >> 8) & 0xffu, WQ_UNIT);
+                                const float Dc = dchild();
+                                const float H0 = wq_h0(QS, L, Dc, smin, s2);
+                                const float w = NLH * (H0 + __builtin_fmaf(Dc, sth, m)) * (1.0f + 0x1p-16f) + 384.0f * m;
+                                okb = !(-b < C0 - w || -b > C1 + w);
+                            }
+                            if (okb)
+                                key[j] = 0.0f;
+                        } else if (risk && !nob && qlb < QS && rkj < INFINITY && !(kbl > best_s)) {
+                            const uint32_t e2 = wd(WN_EXT2 + j);
+                            // the at-risk octree leaves' box widened by m + rho (any t)
+                            const float Mb = m + wq_len(e2 & 0xffu);
+                            const uint32_t r0 = rw[2 * j], r1 = rw[2 * j + 1];   // lo x y z, hi x y z bytes
+                            const float blx = (float)(r0 & 0xffu), bly = (float)((r0 >> 8) & 0xffu),
+                                        blz = (float)((r0 >> 16) & 0xffu), bhx = (float)(r0 >> 24),
+                                        bhy = (float)(r1 & 0xffu), bhz = (float)((r1 >> 8) & 0xffu);
+                            const float umin = fmaxf(fmaxf(__builtin_fmaf(-Mb, aix, __builtin_fmaf(nx_lo ? blx : bhx, sx, bx)),
+                                                           __builtin_fmaf(-Mb, aiy, __builtin_fmaf(ny_lo ? bly : bhy, sy, by))),
+                                                     __builtin_fmaf(-Mb, aiz, __builtin_fmaf(nz_lo ? blz : bhz, sz, bz)));
+                            const float umax = fminf(fminf(__builtin_fmaf(Mb, aix, __builtin_fmaf(nx_lo ? bhx : blx, sx, bx)),
+                                                           __builtin_fmaf(Mb, aiy, __builtin_fmaf(ny_lo ? bhy : bly, sy, by))),
+                                                     __builtin_fmaf(Mb, aiz, __builtin_fmaf(nz_lo ? bhz : blz, sz, bz)));
+                            bool okb = !(umin > __builtin_fmaf(fabsf(umax), SL, umax));
+                            if (okb) {
+                                const float s2 = wq_val_nz((e >> 8) & 0xffu, WQ_UNIT);
+                                const float Dc = dchild();
+                                const float H0 = wq_h0(QS, L, Dc, smin, s2);
+                                const float w = NLH * (H0 + __builtin_fmaf(Dc, sth, m)) * (1.0f + 0x1p-16f) + 384.0f * m;
+                                okb = !(-b < C0 - w || -b > C1 + w);   // N . (o - origin) = -b
+                            }
+                            if (okb)
+                                key[j] = fminf(key[j], fminf(fmaxf(kbl, 0.0f), 3.0e38f));
                         }
-                        if (okb)
-                            key[j] = 0.0f;
-                    } else if (risk && !nob && qlb < QS && rkj < INFINITY && !(kbl > best_s)) {
-                        const uint32_t e2 = wd(WN_EXT2 + j);
-                        // the at-risk octree leaves' box widened by m + rho (any t)
-                        const float Mb = m + wq_len(e2 & 0xffu);
-                        const uint32_t r0 = rw[2 * j], r1 = rw[2 * j + 1];   // lo x y z, hi x y z bytes
-                        const float blx = (float)(r0 & 0xffu), bly = (float)((r0 >> 8) & 0xffu),
-                                    blz = (float)((r0 >> 16) & 0xffu), bhx = (float)(r0 >> 24),
-                                    bhy = (float)(r1 & 0xffu), bhz = (float)((r1 >> 8) & 0xffu);
-                        const float umin = fmaxf(fmaxf(__builtin_fmaf(-Mb, aix, __builtin_fmaf(nx_lo ? blx : bhx, sx, bx)),
-                                                       __builtin_fmaf(-Mb, aiy, __builtin_fmaf(ny_lo ? bly : bhy, sy, by))),
-                                                 __builtin_fmaf(-Mb, aiz, __builtin_fmaf(nz_lo ? blz : bhz, sz, bz)));
-                        const float umax = fminf(fminf(__builtin_fmaf(Mb, aix, __builtin_fmaf(nx_lo ? bhx : blx, sx, bx)),
-                                                       __builtin_fmaf(Mb, aiy, __builtin_fmaf(ny_lo ? bhy : bly, sy, by))),
-                                                 __builtin_fmaf(Mb, aiz, __builtin_fmaf(nz_lo ? bhz : blz, sz, bz)));
-                        bool okb = !(umin > __builtin_fmaf(fabsf(umax), SL, umax));
-                        if (okb) {
-                            const float s2 = wq_val_nz((e >> 8) & 0xffu, WQ_UNIT);
-                            const float Dc = dchild();
-                            const float H0 = wq_h0(QS, L, Dc, smin, s2);
-                            const float w = NLH * (H0 + __builtin_fmaf(Dc, sth, m)) * (1.0f + 0x1p-16f) + 384.0f * m;
-                            okb = !(-b < C0 - w || -b > C1 + w);   // N . (o - origin) = -b
-                        }
-                        if (okb)
-                            key[j] = fminf(key[j], fminf(fmaxf(kbl, 0.0f), 3.0e38f));
                     }
                     // visit order: the entry t of the child's unwidened box (not below the key).  A child
                     // holding ill-conditioned triangles (UV-sphere pole slivers) has a box widened by a

@@ -17,6 +17,8 @@ sc, st = scenes.CONFIGS[name]()
 import ctypes
 from raytracercpp_amd import _lib
 _diag = getattr(_lib.lib(), "rt_diag_wave_steps", None) if hasattr(_lib, "lib") else None
+# the wave node steps whose active lanes all skip case (b) (DESIGN.md 5.10's S)
+_diag_nob = getattr(_lib.lib(), "rt_diag_nob_steps", None) if hasattr(_lib, "lib") else None
 for mode in modes:
     if mode == "whole_line":
         os.environ["RT_SEG"] = "0"
@@ -26,13 +28,19 @@ for mode in modes:
     r.ray_trace()        # builds the octree; the wide BVH and leaf cones build beside it
     r.finish_accel()     # counted frame on the adopted structures
     steps = (ctypes.c_ulonglong * 8)()
+    nob4 = (ctypes.c_ulonglong * 4)()
     if _diag:
         _diag(steps)   # clear
+    if _diag_nob:
+        _diag_nob(nob4)
     r.ray_trace()
     s = r.stats()
     if _diag:
         _diag(steps)
+    if _diag_nob:
+        _diag_nob(nob4)
     st8 = list(steps)
+    nb = list(nob4)
     w = s["work"]
     print(json.dumps({"config": name, "mode": mode, "seg_scale": s["seg_scale"], "primary_rays": s["primary_rays"],
                       "shadow_rays": s["shadow_rays"], "reflection_rays": s["reflection_rays"],
@@ -45,5 +53,8 @@ for mode in modes:
                       "wave_node_steps": st8[0], "uniform_node_steps": st8[1], "wave_leaf_steps": st8[2],
                       "uniform_leaf_steps": st8[3], "node_step_lanes": st8[4], "leaf_step_lanes": st8[5],
                       "distinct_nodes": st8[6], "distinct_leaves": st8[7],
+                      "all_nob_node_steps": nb[0], "all_nob_node_step_lanes": nb[1],
+                      "all_nob_share_of_node_steps": round(nb[0] / max(1, nb[2]), 4),
+                      "all_nob_share_of_node_step_lanes": round(nb[1] / max(1, nb[3]), 4),
                       "simd_efficiency": [round(s["wave_steps"][i + 1] / max(1, 64 * s["wave_steps"][i]), 4)
                                           for i in (0, 3)]}), flush=True)
