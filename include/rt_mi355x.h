@@ -535,6 +535,42 @@ int rt_trace_ray_batch_device(rt_renderer *r, const float *d_orig, const float *
                               int64_t *d_counts, void *hip_stream);
 int rt_get_device_shaded_batches(rt_renderer *r, int64_t calls[2], int64_t rays[2]);
 
+/* The visibility buffer of the current camera on device memory (no reference counterpart).
+ * rt_visibility_device answers, for every pixel of the internal image (render_w x render_h, SSAA applied; row 0 is
+ * NDC y = -1, as everywhere), the closest-hit part of Renderer::trace_ray at depth 0 (renderer.cpp:1008-1040) for
+ * that pixel's camera ray (renderer.cpp:1086-1098).  Nothing is shaded and no shadow ray is traced.  Outputs,
+ * row-major [render_h][render_w], in memory of the handle's device; each may be NULL and is then not written, all
+ * three NULL is RT_EINVAL:
+ *   d_tri_id: the record's source when t > 0.1 (triangle index in caller order, or -2 - k for analytic shape k),
+ *             else -1: exactly the hit_id rt_ray_trace leaves for rt_get_internal;
+ *   d_t:      the record's t (-1 for a fresh record): rt_get_internal's hit_t, bit for bit;
+ *   d_uv:     [..][2] floats, 8-byte aligned (else RT_EINVAL): where d_tri_id >= 0 the record's u, v, bit for bit
+ *             what rt_trace_rays_device writes for that ray; (0, 0) everywhere else.
+ * This holds in every mode (SAH or quick wide tree, before one is resident, exact mode, RT_WBVH=0, enable_bvh 0,
+ * analytic shapes).  No shading setting is read: shading method, textures, sky, reflective materials, enable_ssao,
+ * max_recursion_depth; hybrid_rasterization_tracing is ignored, as rt_ray_trace ignores it.  The scene is checked
+ * only as far as the query reads it, as for rt_is_shadowed_device: no material or texture is needed.
+ * Over a resident wide tree, with enable_bvh on and no analytic shape, the launch runs the frames' primary query
+ * with their tile mask and per-block entry sets (the entry sets from a stream's second
+ * launch in a row with one camera on), without the frame's shading and shadow query.
+ * The contract is rt_trace_rays_device's: the work runs on hip_stream (NULL: the null stream) in its order, only
+ * the caller's memory is written, the host does not wait for the GPU, whatever later replaces what the kernel reads
+ * and rt_destroy wait for it, and the stream may be destroyed right after the call.  The call may block for what a
+ * frame would block on (a pending rebuild).  Unlike the ray queries it may allocate device memory: each stream has
+ * its own tile-queue counters and tile mask, allocated at the stream's first call and when the render size grows;
+ * up to 8 streams keep theirs, a ninth takes over the least recently used stream's once that stream's last launch
+ * is done (the host waits for it).  Launches on different streams run concurrently, among themselves and with band
+ * launches; rt_tile_mask, rt_tile_starts, rt_tile_lists, rt_band_counters, rt_kernel_times, rt_band_costs and
+ * rt_get_stats report what they would report without the call.
+ * Every refusal happens before any launch: RT_EINVAL for a pointer that is not memory of the handle's device, a
+ * misaligned d_uv, no output; the errors a frame reports come back with the same codes.  With rt_set_devices the
+ * call runs on the handle's own device.
+ * rt_get_device_visibility: calls[0..1] / pixels[0..1] = launches of the kernel's two instances since rt_create
+ * ([0] the fast one over the wide tree, [1] the generic one) and their pixels; used[0] = launches that were given a
+ * tile mask, used[1] = launches that were given entry sets. */
+int rt_visibility_device(rt_renderer *r, int32_t *d_tri_id, float *d_t, float *d_uv, void *hip_stream);
+int rt_get_device_visibility(rt_renderer *r, int64_t calls[2], int64_t pixels[2], int64_t used[2]);
+
 /* Renderer::trace_ray(ray, hit_info, current_recursion_depth, intersection_found)
  * (renderer.h:144, renderer.cpp:1008-1066) for n arbitrary rays (origins / directions [n][3]),
  * each with a fresh HitInfo: rgba [n][4] = the Color trace_ray returns (shading, shadow ray,

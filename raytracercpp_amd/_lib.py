@@ -150,6 +150,8 @@ SIGNATURES = {
     "rt_trace_ray_batch_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_get_device_shaded_batches": (C.c_int, [_H, _i64p, _i64p]),
+    "rt_visibility_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_get_device_visibility": (C.c_int, [_H, _i64p, _i64p, _i64p]),
     "rt_trace_ray":(C.c_int, [_H, _f32p, _f32p, C.c_int64, C.c_int32, _f32p, _i32p, _f32p, _u8p, _u8p]),
     "rt_wide_query": (C.c_int, [_H, _f32p, _f32p, C.c_int64, C.c_int32, _f32p, _f32p, _i32p, _i32p, _f32p, _f32p, _f32p,
                                 _u8p]),
@@ -204,6 +206,8 @@ SHADED_QUERIES = ("rt_trace_ray_device", "rt_get_device_shaded_queries")
 SHADED_BATCHES = ("rt_trace_ray_batch_device", "rt_get_device_shaded_batches")
 # the tile lists' read-back, likewise (an A/B run against the parent commit's library)
 TILE_LISTS = ("rt_tile_lists",)
+# the visibility buffer on device memory, likewise
+VISIBILITY = ("rt_visibility_device", "rt_get_device_visibility")
 
 _lib = None
 
@@ -228,7 +232,7 @@ def lib():
             pass
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            if (name in GEOMETRY_INPUT + RAY_QUERIES + SHADED_QUERIES + SHADED_BATCHES + TILE_LISTS and
+            if (name in GEOMETRY_INPUT + RAY_QUERIES + SHADED_QUERIES + SHADED_BATCHES + TILE_LISTS + VISIBILITY and
                     os.environ.get("RT_LIB_PATH") and not hasattr(L, name)):
                 continue
             fn = getattr(L, name)
@@ -458,6 +462,40 @@ def device_shade_outs(out, n, device):
     for k, _, _ in given:
         _device_place(out[k], k, device)
     return [out[k].data_ptr() if k in out else None for k, _, _ in SHADE_OUT]
+
+
+# the outputs of Renderer.visibility_device in the C call's order: (key, dtype, trailing dimension; None: [rh, rw])
+VISIBILITY_OUT = (("tri_id", "int32", None), ("t", "float32", None), ("uv", "float32", 2))
+
+
+def device_visibility_outs(out, rw, rh, device):
+    """The checks of Renderer.visibility_device on its ``out`` dict: any non-empty subset of VISIBILITY_OUT's keys,
+    each a contiguous torch tensor of exactly [rh, rw] (uv: [rh, rw, 2]) and its dtype on the GPU with index
+    ``device``; what every tensor is (layout included) before where any lies, so those mistakes show without a
+    GPU; the three pointers, None for a key left out."""
+    import torch
+
+    if not isinstance(out, dict):
+        raise TypeError(f"out: a dict of torch tensors is needed, not {type(out).__name__}")
+    unknown = sorted(set(out) - {k for k, _, _ in VISIBILITY_OUT})
+    if unknown:
+        raise ValueError(f"out: unknown key {unknown[0]!r}")
+    given = [(k, getattr(torch, dt), c) for k, dt, c in VISIBILITY_OUT if k in out]
+    if not given:
+        raise ValueError("out: at least one of tri_id, t, uv is needed")
+    for k, dtype, c in given:
+        t = out[k]
+        shape = (rh, rw) if c is None else (rh, rw, c)
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{k}: a torch tensor on the GPU is needed, not {type(t).__name__}")
+        if t.dtype != dtype:
+            raise TypeError(f"{k}: dtype {t.dtype}, {dtype} is needed")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{k}: shape {tuple(t.shape)}, {list(shape)} is needed")
+        _contiguous(t, k)
+    for k, _, _ in given:
+        _device_place(out[k], k, device)
+    return [out[k].data_ptr() if k in out else None for k, _, _ in VISIBILITY_OUT]
 
 
 def load_obj(path, xform, mat_offset=0):

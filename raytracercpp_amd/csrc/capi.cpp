@@ -515,6 +515,19 @@ int rt_get_device_shaded_batches(rt_renderer* r, int64_t calls[2], int64_t rays[
         return RT_OK;
     });
 }
+int rt_visibility_device(rt_renderer* r, int32_t* d_tri_id, float* d_t, float* d_uv, void* hip_stream)
+{
+    return guarded(R(r), [&] { return R(r)->visibility_device(d_tri_id, d_t, d_uv, reinterpret_cast<hipStream_t>(hip_stream)); });
+}
+int rt_get_device_visibility(rt_renderer* r, int64_t calls[2], int64_t pixels[2], int64_t used[2])
+{
+    return guarded(R(r), [&] {
+        if (!calls || !pixels || !used)
+            return RT_EINVAL;
+        R(r)->device_visibility(calls, pixels, used);
+        return RT_OK;
+    });
+}
 int rt_wide_query(rt_renderer* r, const float* orig, const float* dir, int64_t n, int32_t kind, float* o_out,
                   float* d_out, int32_t* status, int32_t* tri_id, float* t, float* u, float* v, uint8_t* shadowed)
 {

@@ -1337,7 +1337,9 @@ __device__ __forceinline__ void shapes_closest(const KParams& P, v3 o, v3 d, Rec
 // fin is the caller's HitInfo; returns the source (-1 none, >=0 triangle, -2-k shape k).
 // With the wide BVH (P.wnodes), a certified query takes its answer; one it cannot certify
 // is traced through the octree here.
-template <bool PLAIN = false, int G = 1, bool OCT = false>
+// COPY: a caller's own instance of the same code (visibility_kernel<true>), as is_shadowed's: one more call of the
+// plain frame pixel's instance took it out of line there and made the frame kernels spill.
+template <bool PLAIN = false, int G = 1, bool OCT = false, int COPY = 0>
 __device__ int closest_hit(const KParams& P, v3 o, v3 d, Rec& fin, uint2* lv, int bidx = -1)
 {
     Rec local = rec_fresh();
@@ -3978,6 +3980,73 @@ __global__ __launch_bounds__(256) void wide_gather_kernel(const GTri* __restrict
     wmeta[k] = make_uint4((uint32_t)s, leaf_of_slot[s], (uint32_t)id, (uint32_t)tri_mat[id]);
 }
 
+// The visibility buffer of the current camera (rt_visibility_device): per pixel of the internal
+// image the closest-hit part of trace_ray at depth 0 -- the record's source where t > 0.1 (else -1), its t, and
+// its u, v where the source is a triangle (else 0, 0) -- into the caller's device buffers, each of which may be
+// null.  The frame kernel's structure (persistent waves, one per 8 x 8 tile from the sharded queue over
+// P.counters, camera_dir) without a pixel to shade: no shadow query, nothing parked in LDS, no heavy-tile order,
+// split parts, tile lists or tile costs (the host leaves those fields null).
+// FAST (the host: a wide tree serves queries, enable_bvh on, no analytic shape): the plain frame kernel's primary
+// query, closest_hit<true>, with the launch's tile mask (a clear tile is written without a ray, as
+// fill_masked_tile writes it for frames) and its entry sets; else the generic closest_hit<false> (the octree walk
+// before a tree is resident, exact mode, the brute-force loop, shapes), which takes neither.
+// KParams is the first argument: closest_hit<true>'s octree fallback reads it through kernel_params().
+#ifndef RT_OCC_VIS
+#define RT_OCC_VIS RT_OCC_PLAIN   // lds_bytes(P, true) keeps three blocks per CU whatever the registers allow
+#endif
+template <bool FAST>
+__global__ __launch_bounds__(BLOCK, FAST ? RT_OCC_VIS : RT_OCC_PLAIN) void visibility_kernel(KParams P_arg,
+                                                                                             int32_t* __restrict__ out_id,
+                                                                                             float* __restrict__ out_t,
+                                                                                             float2* __restrict__ out_uv)
+{
+    (void)P_arg;
+    auto kp = __builtin_amdgcn_kernarg_segment_ptr();
+    uint2* lv = lane_stack();
+    const int lane = threadIdx.x & 63;
+    tile_queue_init();
+    for (;;) {
+        auto kpl = kp;
+        asm volatile("" : "+s"(kpl));   // (the loop's loads depend on it: not hoisted, as in the frame kernels)
+        const KParams& P = *reinterpret_cast<const KParams*>((const void*)kpl);
+        const int tile = tile_queue_next<false>(P);
+        if (tile < 0)
+            break;
+        int tx, ty;
+        tile_xy(P, tile, tx, ty);
+        const int px = tx * 8 + (lane & 7);
+        const int py = ty * 8 + (lane >> 3);
+        if (px >= P.rw || py >= P.rh)
+            continue;
+        const size_t o = (size_t)py * P.rw + px;
+        int id = -1;
+        float t = rec_fresh().t, u = 0.0f, v = 0.0f;
+        bool masked = false;
+        if (FAST && P.tile_mask) {
+            // (the tile is one block of the mask: every lane reads the same bit)
+            const uint32_t mw = ldg(P.tile_mask + (size_t)(py >> 3) * (size_t)P.mask_wpr + (size_t)(px >> 8));
+            masked = !__ballot((mw >> ((px >> 3) & 31)) & 1u);
+        }
+        if (!masked) {
+            const v3 cam = mk(P.cam_pos[0], P.cam_pos[1], P.cam_pos[2]);
+            const v3 rd = camera_dir(P, px, py, cam);
+            Rec fin = rec_fresh();
+            const int src = closest_hit<FAST, 1, false, FAST ? 1 : 0>(P, cam, rd, fin, lv, FAST ? tile_start_index(P, px, py) : -1);
+            t = fin.t;
+            if (fin.t > 0.1f) {
+                id = src;
+                if (src >= 0) {
+                    u = fin.u;
+                    v = fin.v;
+                }
+            }
+        }
+        if (out_id) out_id[o] = id;
+        if (out_t) out_t[o] = t;
+        if (out_uv) out_uv[o] = make_float2(u, v);
+    }
+}
+
 // dynamic LDS of the traversal kernels: the octree level stack, or the wide-BVH stack
 // (the same memory; a lane uses one at a time)
 // plain_pixel: the launch runs trace_pixel<false, true> (the plain ray_trace_kernel instances and their
@@ -4044,6 +4113,25 @@ hipError_t rt_launch_shadow_points(const rt::KParams* P, const float* point, con
     size_t lds = rt::lds_bytes(*P);
     hipLaunchKernelGGL(rt::shadow_points_kernel, dim3((n + rt::BLOCK - 1) / rt::BLOCK), dim3(rt::BLOCK), lds, stream, *P,
                        point, normal, n, light[0], light[1], light[2], shadowed);
+    return hipGetLastError();
+}
+
+hipError_t rt_launch_visibility(const rt::KParams* P, bool fast, int32_t* id, float* t, float* uv, hipStream_t stream)
+{
+    const int tiles = P->tiles_x * P->tiles_y;
+    if (tiles < 1)
+        return hipSuccess;
+    const int blocks = (tiles + rt::WAVES_PER_BLOCK - 1) / rt::WAVES_PER_BLOCK;
+    // persistent grids: the fast instance's is its residency (RT_OCC_VIS blocks per CU: lds_bytes(P, true) allows
+    // three), the generic instance's at most what fills every CU
+    const int cap = fast ? P->max_blocks / 8 * RT_OCC_VIS : P->max_blocks;
+    const dim3 grid((unsigned)(P->max_blocks > 0 ? std::max(1, std::min(blocks, cap)) : blocks));
+    const size_t lds = rt::lds_bytes(*P, fast);
+    float2* uv2 = reinterpret_cast<float2*>(uv);
+    if (fast)
+        hipLaunchKernelGGL(rt::visibility_kernel<true>, grid, dim3(rt::BLOCK), lds, stream, *P, id, t, uv2);
+    else
+        hipLaunchKernelGGL(rt::visibility_kernel<false>, grid, dim3(rt::BLOCK), lds, stream, *P, id, t, uv2);
     return hipGetLastError();
 }
 

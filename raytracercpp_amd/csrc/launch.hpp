@@ -51,6 +51,11 @@ RT_LAUNCH rt_launch_closest_rays(const rt::KParams* P, const float* o, const flo
                                  float* u, float* v, uint8_t* ret, int64_t* counts, hipStream_t stream);
 RT_LAUNCH rt_launch_shadow_points(const rt::KParams* P, const float* point, const float* normal, int n,
                                   const float light[3], uint8_t* shadowed, hipStream_t stream);
+// the visibility buffer of P's camera over the caller's device memory (rt_visibility_device): id / t [rh][rw], uv
+// [rh][rw][2] (8-byte aligned), each may be null.  fast: the plain frame kernel's primary query with P's tile mask
+// and entry sets (the host: P->wnodes, enable_bvh, no analytic shape), else the generic one.  P->counters: the
+// launch's own zeroed counter block; no heavy list, tile costs or tile lists in P
+RT_LAUNCH rt_launch_visibility(const rt::KParams* P, bool fast, int32_t* id, float* t, float* uv, hipStream_t stream);
 // the shaded query over device memory (rt_trace_ray_device; rt_trace_ray's staged arrays): inst is rt::SHADE_*;
 // every output but rgba may be null; the fill writes what trace_ray returns past max_recursion_depth
 RT_LAUNCH rt_launch_shade_rays(const rt::KParams* P, int inst, const float* o, const float* d, int n,

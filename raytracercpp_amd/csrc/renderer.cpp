@@ -207,6 +207,8 @@ Renderer::~Renderer()
         if (e) hipEventDestroy(e);
     for (auto& b : band_slot_)
         b.fence.destroy();
+    for (auto& v : vis_slot_)
+        v.fence.destroy();
     if (fence_stream_) hipStreamDestroy(fence_stream_);
     if (stream_) hipStreamDestroy(stream_);
     for (hipEvent_t ev : display_ev_)
@@ -2479,19 +2481,25 @@ int Renderer::prepare_risk(KParams& P, hipStream_t stream)
 // its frames in flight.  No mask (nullptr) for anything but the plain kernel over the wide BVH with an
 // affine camera; RT_TILE_MASK=0: none.  With the mask go the launch's tile lists (KParams::list_off, tile_lists.hpp,
 // DESIGN.md 5.14; layout_key: the band list's hash, as prepare_heavy's); RT_TILE_LIST=0: none.
-int Renderer::prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M, uint64_t layout_key)
+// visibility (visibility_device, whose M is its own stream slot's): the visibility kernel's fast instance runs the
+// plain kernel's primary query whatever the scene's shading is, so the condition is that instance's (a wide tree,
+// enable_bvh, no analytic shape); it takes no lists, and what the frames' getters report stays as it is.
+int Renderer::prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M, uint64_t layout_key, bool visibility)
 {
     P.tile_mask = nullptr;
     P.mask_wpr = 0;
     P.tile_start = nullptr;
     P.start_bw = 0;
     P.list_off = 0;
-    mask_last_ = nullptr;
-    starts_last_ = false;
-    lists_last_ = false;
-    mask_seen_ = true;
-    if (!knobs_.tile_mask || !P.wnodes || !P.plain || P.has_reflection || P.zbuf || P.nbuf || wide_.nn <= 0 || !wide_.b_links.p ||
-        s_.hybrid_rasterization_tracing)
+    if (!visibility) {
+        mask_last_ = nullptr;
+        starts_last_ = false;
+        lists_last_ = false;
+        mask_seen_ = true;
+    }
+    const bool takes_mask = visibility ? P.enable_bvh && P.nshape == 0
+                                       : P.plain && !P.has_reflection && !P.zbuf && !P.nbuf && !s_.hybrid_rasterization_tracing;
+    if (!knobs_.tile_mask || !P.wnodes || !takes_mask || wide_.nn <= 0 || !wide_.b_links.p)
         return RT_OK;
     WMaskCam C = wbvh_mask_cam(P.proj_inv, P.cam_to_world, P.proj_mode, P.proj_w, P.c2w_affine, P.cam_pos, P.light,
                                P.scene_scale, W_QS_CLOSEST, P.rw, P.rh);
@@ -2515,7 +2523,7 @@ int Renderer::prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M, uint64_t
     // has to grow for them loses its words
     const int ntiles = P.tiles_x * P.tiles_y;
     const size_t list_off = ((size_t)C.bh * C.wpr + 3) / 4 * 4;   // (KParams::list_off: 4-byte words, an int32_t)
-    const bool lists = knobs_.tile_list && ntiles > 0 && list_off + tile_lists_words(ntiles) <= (size_t)INT32_MAX;
+    const bool lists = !visibility && knobs_.tile_list && ntiles > 0 && list_off + tile_lists_words(ntiles) <= (size_t)INT32_MAX;
     const size_t need = lists ? (list_off + tile_lists_words(ntiles)) * 4 : (size_t)C.bh * C.wpr * 4;
     if (need > M.words.bytes)
         M.cut_gen = 0;
@@ -2547,6 +2555,13 @@ int Renderer::prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M, uint64_t
     }
     P.tile_mask = M.words.as<uint32_t>();
     P.mask_wpr = C.wpr;
+    if (visibility) {   // (no lists, and mask_last_ / starts_last_ / lists_slot_ are the frames')
+        if (M.starts_valid) {
+            P.tile_start = M.starts.as<uint4>();
+            P.start_bw = C.bw;
+        }
+        return RT_OK;
+    }
     if (M.use_gen != cut_gen_) {   // another tree: decide again
         M.use_gen = cut_gen_;
         M.list_use = -1;
@@ -2858,6 +2873,76 @@ int Renderer::is_shadowed_device(const float* d_point, const float* d_normal, in
     return end_ray_query(Q_SHADOW, n, stream);
 }
 
+// The visibility buffer of the current camera (rt_visibility_device).  The ray queries' start and end
+// (the pointer check, the scene as a frame brings it up to date, the risk words, query_fence_), and between them
+// what a frame launch prepares, from a slot of the launching stream's own: the tile queue's counter block and the
+// mask of that stream's last camera (prepare_mask's visibility condition).  Nothing of the band slots, the tile
+// costs or the frames' reporting moves.
+int Renderer::visibility_device(int32_t* d_id, float* d_t, float* d_uv, hipStream_t stream)
+{
+    if (!d_id && !d_t && !d_uv)
+        return fail(RT_EINVAL, "visibility_device: no output");
+    if (reinterpret_cast<uintptr_t>(d_uv) & 7u)
+        return fail(RT_EINVAL, "visibility_device: d_uv is not 8-byte aligned");
+    int rw, rh;
+    render_size(rw, rh);
+    const int64_t npx = (int64_t)rw * rh;
+    if (rw <= 0 || rh <= 0)
+        return fail(RT_EINVAL, "visibility_device: bad arguments");
+    const void* const ptrs[] = {d_id, d_t, d_uv};
+    KParams P;
+    int rc = begin_ray_query("visibility_device", ptrs, 3, 0, npx, stream, P);
+    if (rc != RT_OK)
+        return rc;
+    hipError_t e;
+    uintptr_t streams[VIS_SLOTS];
+    uint64_t used[VIS_SLOTS];
+    for (int i = 0; i < vis_nslots_; i++) {
+        streams[i] = reinterpret_cast<uintptr_t>(vis_slot_[i].stream);
+        used[i] = vis_slot_[i].used;
+    }
+    const VisPick pick = vis_pick_slot(streams, used, vis_nslots_, VIS_SLOTS, reinterpret_cast<uintptr_t>(stream));
+    VisSlot& S = vis_slot_[pick.slot];
+    if (pick.fresh) {
+        if ((e = S.fence.create()) != hipSuccess)
+            return hip_fail(e, "hipEventCreate");
+        vis_nslots_++;
+    } else if (pick.recycled) {
+        // a ninth stream: the least recently used slot, once its last launch is done (its own fence; the stream it
+        // ran on may no longer exist).  The words are another camera's stream's: computed again
+        if ((e = S.fence.sync()) != hipSuccess)
+            return hip_fail(e, "visibility_device: recycling a stream slot");
+        S.mask.cut_gen = 0;
+    } else if ((e = S.fence.wait_on(stream)) != hipSuccess)
+        // (the stream's own slot: its earlier launches come first by the stream's order, unless the handle is a new
+        // stream's that took a destroyed one's value -- then by this)
+        return hip_fail(e, "hipStreamWaitEvent (visibility slot)");
+    S.stream = stream;
+    S.used = ++vis_uses_;
+    if ((e = S.counters.reserve(NCOUNTER_WORDS * 8)) != hipSuccess)
+        return hip_fail(e, "hipMalloc (counters)");
+    P.band_rows = P.rh;
+    P.nranks = 1;
+    P.rank = 0;
+    P.local_rows = P.rh;
+    P.tiles_x = (P.rw + 7) / 8;
+    P.tiles_y = (P.rh + 7) / 8;
+    P.counters = S.counters.as<unsigned long long>();
+    // (fill_params left the heavy list, the tile costs and their sums, and the lists' offset null)
+    const bool fast = P.wnodes && P.enable_bvh && P.nshape == 0;
+    if (fast && (rc = prepare_mask(P, stream, S.mask, 0, true)) != RT_OK)
+        return rc;
+    if ((e = hipMemsetAsync(S.counters.p, 0, NCOUNTER_WORDS * 8, stream)) != hipSuccess)
+        return hip_fail(e, "hipMemsetAsync");
+    if ((e = rt_launch_visibility(&P, fast, d_id, d_t, d_uv, stream)) != hipSuccess)
+        return hip_fail(e, "visibility_kernel launch");
+    if ((e = S.fence.record(stream, fence_stream_)) != hipSuccess)
+        return hip_fail(e, "hipEventRecord");
+    vis_used_[0] += P.tile_mask != nullptr;
+    vis_used_[1] += P.tile_start != nullptr;
+    return end_ray_query(fast ? Q_VISIBILITY_FAST : Q_VISIBILITY_GENERIC, npx, stream);
+}
+
 // the counters of 'count' kinds from 'first' on (the rt_get_device_* getters)
 static void copy_kinds(const int64_t* from_calls, const int64_t* from_rays, int first, int count, int64_t* calls,
                        int64_t* rays)
@@ -2881,8 +2966,16 @@ void Renderer::device_shaded_batches(int64_t calls[2], int64_t rays[2]) const
     copy_kinds(query_calls_, query_rays_, Q_BATCH_ENGINE, 2, calls, rays);
 }
 
+void Renderer::device_visibility(int64_t calls[2], int64_t pixels[2], int64_t used[2]) const
+{
+    copy_kinds(query_calls_, query_rays_, Q_VISIBILITY_FAST, 2, calls, pixels);
+    used[0] = vis_used_[0];
+    used[1] = vis_used_[1];
+}
+
 static_assert(Q_SHADOW == Q_CLOSEST + 1 && Q_SHADED_GENERIC == Q_SHADED_PLAIN + SHADE_GENERIC &&
-                  Q_SHADED_REFL == Q_SHADED_PLAIN + SHADE_REFL && Q_BATCH_DELEGATED == Q_BATCH_ENGINE + 1,
+                  Q_SHADED_REFL == Q_SHADED_PLAIN + SHADE_REFL && Q_BATCH_DELEGATED == Q_BATCH_ENGINE + 1 &&
+                  Q_VISIBILITY_GENERIC == Q_VISIBILITY_FAST + 1,
               "the getters report runs of kinds, the shaded ones in SHADE_*'s order");
 
 int Renderer::begin_shaded_query(const char* what, const ShadeRays& q, hipStream_t stream, KParams& P, bool& launch,

@@ -22,6 +22,7 @@
 #include "octree.hpp"
 #include "tile_lists.hpp"
 #include "tri_geometry.hpp"
+#include "vis_slots.hpp"
 #include "wbvh.hpp"
 #include "wide_layout.hpp"
 
@@ -202,6 +203,8 @@ enum QueryKind {
     Q_SHADED_REFL,
     Q_BATCH_ENGINE,      // trace_ray_batch_device through the frame engine
     Q_BATCH_DELEGATED,   // ... handed to trace_ray_device's code (counted there too)
+    Q_VISIBILITY_FAST,     // visibility_device by instance of visibility_kernel (the "rays": pixels)
+    Q_VISIBILITY_GENERIC,
     Q_KINDS,
     Q_NONE = -1,         // nothing was launched for the scene's rays: an empty call, or the fill past the depth limit
 };
@@ -335,6 +338,15 @@ public:
     // its calls and rays since rt_create: [0] through the engine, [1] handed to trace_ray_device
     // (rt_get_device_shaded_batches)
     void device_shaded_batches(int64_t calls[2], int64_t rays[2]) const;
+    // The visibility buffer of the current camera into memory of device_, on the caller's stream
+    // (rt_visibility_device): per pixel of the internal image trace_ray's closest hit at depth 0 --
+    // the source ray_trace leaves in hit_id, the record's t, and u / v where the source is a triangle.  Each output
+    // may be null.  The ray queries' contract (query_fence_ follows the launch, the host does not wait), with a
+    // slot of per-stream state (vis_slot_) that a stream's first call allocates.
+    int visibility_device(int32_t* d_id, float* d_t, float* d_uv, hipStream_t stream);
+    // its launches and pixels since rt_create by instance (fast, generic), and the launches that were given a tile
+    // mask / entry sets (rt_get_device_visibility)
+    void device_visibility(int64_t calls[2], int64_t pixels[2], int64_t used[2]) const;
     // the frames' wide-BVH query and its status over n host rays (rt_wide_query)
     int wide_query(const float* orig, const float* dir, int64_t n, int kind, float* o_out, float* d_out,
                    int32_t* status, int32_t* id, float* t, float* u, float* v, uint8_t* shadow);
@@ -386,6 +398,7 @@ private:
     // last launch on any stream: fence_stream_ runs in order, so the last record() comes after every earlier one.
     Fence query_fence_;
     int64_t query_calls_[Q_KINDS] = {}, query_rays_[Q_KINDS] = {};
+    int64_t vis_used_[2] = {};   // visibility launches given a tile mask, entry sets
     // before a query launch on 'stream': the count and the pointers (n_required of them must not be null when
     // n > 0; each must be memory of device_; nptrs 0: the renderer's own staging buffer, nothing to check), the
     // scene as a frame brings it up to date (shaded: validated first, with rt_trace_ray's codes and texts), P with
@@ -603,7 +616,10 @@ private:
     bool lists_last_ = false;  // the last launch was given tile lists (mask_last_'s)
     bool starts_last_ = false; // the last launch was given entry sets (mask_last_->starts)
     Fence cut_fence_;
-    int prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M, uint64_t layout_key = 0);
+    // visibility (visibility_device): the mask and the entry sets alone, under the visibility kernel's weaker
+    // condition (a wide tree, enable_bvh, no analytic shape: nothing of the shading matters), and nothing of what
+    // the frames' getters report (mask_last_, starts_last_, lists_last_, lists_slot_, mask_seen_) moves
+    int prepare_mask(KParams& P, hipStream_t stream, MaskSlot& M, uint64_t layout_key = 0, bool visibility = false);
     DevBuf d_dbg_;                          // diagnostic per-wave records (RT_DEBUG_WAVES)
     bool ssao_ready_ = false;   // the buffers hold the last frame's z / normals
     // raster path: per-triangle piece counts / offsets, the piece table and its texcoords, the z-key
@@ -673,6 +689,19 @@ private:
     BandSlot band_slot_[BAND_SLOTS];
     int band_nslots_ = 0, band_last_ = -1;
     uint64_t band_uses_ = 0;
+    // visibility_device: per launching stream the tile queue's counter block and the mask of that stream's last
+    // camera, so that launches on different streams run concurrently; none of it is the band slots' (band_last_,
+    // the tile costs and the slots' masks belong to frames).  vis_slots.hpp picks the slot.
+    struct VisSlot {
+        hipStream_t stream = nullptr;
+        DevBuf counters;
+        MaskSlot mask;
+        Fence fence;         // follows the slot's last launch
+        uint64_t used = 0;   // vis_uses_ at the slot's last launch
+    };
+    VisSlot vis_slot_[VIS_SLOTS];
+    int vis_nslots_ = 0;
+    uint64_t vis_uses_ = 0;
     // event ring for render_bands_device kernel timing
     static constexpr int EV_RING = 256;
     std::vector<hipEvent_t> ring_;

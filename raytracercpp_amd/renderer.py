@@ -473,6 +473,35 @@ class Renderer:
         self._call("rt_get_device_ray_queries", ptr(calls, i64p), ptr(rays, i64p))
         return (int(calls[0]), int(calls[1])), (int(rays[0]), int(rays[1]))
 
+    def visibility_device(self, out=None, stream=None):
+        """rt_visibility_device: the visibility buffer of the current camera, in the order of ``stream`` (a torch
+        stream; default the current one) and without a host wait -> dict(tri_id int32 [rh, rw], t float32 [rh, rw],
+        uv float32 [rh, rw, 2]) of torch tensors on this renderer's GPU, rh x rw the internal image (SSAA applied):
+        per pixel the hit_id and hit_t ray_trace leaves for get_internal, and the hit's barycentrics where tri_id
+        >= 0 (else 0, 0).  Nothing is shaded.  out: such a dict to write into, any non-empty subset of the keys:
+        only those are written and returned; else three new tensors."""
+        import torch
+        st = self.stats()
+        rw, rh = st["render_width"], st["render_height"]
+        stream = self._ray_stream(stream)
+        if out is None:
+            with torch.cuda.stream(stream):
+                out = {k: torch.empty((rh, rw) if c is None else (rh, rw, c), dtype=getattr(torch, dt),
+                                      device=torch.device("cuda", self.device))
+                       for k, dt, c in _lib.VISIBILITY_OUT}
+        ptrs = _lib.device_visibility_outs(out, rw, rh, self.device)
+        self._call("rt_visibility_device", *[C.c_void_p(p) for p in ptrs], self._stream_ptr(stream, self.device))
+        return out
+
+    def device_visibility(self):
+        """rt_get_device_visibility -> (calls, pixels, used): visibility_device's launches of the fast [0] and the
+        generic [1] kernel instance since the renderer was created and their pixels; used: the launches that were
+        given a tile mask [0] and entry sets [1]."""
+        calls, pixels, used = np.zeros(2, np.int64), np.zeros(2, np.int64), np.zeros(2, np.int64)
+        i64p = C.POINTER(C.c_int64)
+        self._call("rt_get_device_visibility", ptr(calls, i64p), ptr(pixels, i64p), ptr(used, i64p))
+        return tuple(int(c) for c in calls), tuple(int(p) for p in pixels), tuple(int(u) for u in used)
+
     def trace_ray_device(self, orig, dirs, current_recursion_depth=0, first_ray=0, out=None, counts=None, stream=None):
         """rt_trace_ray_device: trace_ray (shaded) for rays in GPU memory, in the order of ``stream`` (a torch
         stream; default the current one) and without a host wait -> dict(rgba float32 [n, 4], hit_src int32,
