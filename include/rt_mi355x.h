@@ -467,6 +467,38 @@ int rt_is_shadowed_device(rt_renderer *r, const float *d_point, const float *d_n
                           uint8_t *d_shadowed, void *hip_stream);
 int rt_get_device_ray_queries(rt_renderer *r, int64_t calls[2], int64_t rays[2]);
 
+/* Ray-segment queries on device memory (no reference counterpart): is anything hit before
+ * d_tmax[i] along ray i, and if so what.  The definition goes through rt_trace_rays_device: let (id, t, u, v,
+ * ret) be what that call writes for ray i in the same renderer state, and hit_i = ret != 0 && t < d_tmax[i], a
+ * float32 comparison: strict, and false for a NaN on either side.
+ * rt_occluded_device writes d_occluded[i] = hit_i (1 or 0).
+ * rt_trace_segments_device writes those five values bit for bit where hit_i holds and -1, -1.0f, 1.0f, 0.0f, 0
+ * everywhere else, whatever stale record the whole-line query left.
+ * d_tmax: [n] floats in memory of the handle's device; NULL means +inf for every ray.  Triangles only, as
+ * rt_trace_rays_device: analytic shapes are not part of BVH::intersect and are ignored; compute_shadows is not
+ * read.  This holds in every mode rt_trace_rays_device covers (the SAH or the quick tree, before one is
+ * resident, exact mode, RT_WBVH=0, RT_SEG=0, enable_bvh 0, a scene with analytic shapes, non-finite rays).
+ * The wide query stops at d_tmax[i] instead of walking the ray's whole line; so does its fallback, the octree
+ * walk, with RT_SEG_OCTREE=1.  That switch is off by default and is the one exception to the definition: its
+ * form assumes that no grazing hit is reported outside its triangle's volumes, so with
+ * RT_SEG_OCTREE=1 the answer may differ from the definition for a ray the wide query does not certify whose
+ * segment ends within an ulp of a grazing hit (14 of 20,000 rays of the grazing-plane stress set).
+ * d_counts (int64 [2] in device memory, or NULL; the caller zeroes it): [0] += the rays the certified wide query
+ * decided, [1] += the rays that went through the octree walk or the brute-force loop; one call's increments
+ * sum to n.
+ * Everything else is rt_trace_rays_device's contract: the stream order, no host wait, no allocation, every
+ * pointer (d_tmax and d_counts included) checked to be memory of the handle's device, the wait of whatever
+ * replaces what the kernel reads, RT_EINVAL for a null required pointer with n > 0, n < 0 or n > 2^30, and
+ * n == 0: RT_OK with no launch.
+ * rt_get_device_segment_queries: calls[0..1] = launches of the two queries (occluded, segments) since
+ * rt_create, rays[0..1] = the rays given to them. */
+int rt_occluded_device(rt_renderer *r, const float *d_orig, const float *d_dir, const float *d_tmax, int64_t n,
+                       uint8_t *d_occluded, int64_t *d_counts, void *hip_stream);
+int rt_trace_segments_device(rt_renderer *r, const float *d_orig, const float *d_dir, const float *d_tmax, int64_t n,
+                             int32_t *d_tri_id, float *d_t, float *d_u, float *d_v, uint8_t *d_ret,
+                             int64_t *d_counts, void *hip_stream);
+int rt_get_device_segment_queries(rt_renderer *r, int64_t calls[2], int64_t rays[2]);
+
 /* The shaded query on device memory (no reference counterpart).
  * rt_trace_ray_device is rt_trace_ray (below) with every array in memory of the handle's device: d_orig / d_dir
  * [n][3] floats in; d_rgba [n][4] floats out (required, 16-byte aligned: else RT_EINVAL); d_hit_src / d_t /

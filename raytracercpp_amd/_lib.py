@@ -144,6 +144,11 @@ SIGNATURES = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_is_shadowed_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, _f32p, C.c_void_p, C.c_void_p]),
     "rt_get_device_ray_queries": (C.c_int, [_H, _i64p, _i64p]),
+    "rt_occluded_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    "rt_trace_segments_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rt_get_device_segment_queries": (C.c_int, [_H, _i64p, _i64p]),
     "rt_trace_ray_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rt_get_device_shaded_queries": (C.c_int, [_H, _i64p, _i64p]),
@@ -208,6 +213,8 @@ SHADED_BATCHES = ("rt_trace_ray_batch_device", "rt_get_device_shaded_batches")
 TILE_LISTS = ("rt_tile_lists",)
 # the visibility buffer on device memory, likewise
 VISIBILITY = ("rt_visibility_device", "rt_get_device_visibility")
+# the ray-segment queries, likewise
+SEGMENT_QUERIES = ("rt_occluded_device", "rt_trace_segments_device", "rt_get_device_segment_queries")
 
 _lib = None
 
@@ -232,8 +239,8 @@ def lib():
             pass
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            if (name in GEOMETRY_INPUT + RAY_QUERIES + SHADED_QUERIES + SHADED_BATCHES + TILE_LISTS + VISIBILITY and
-                    os.environ.get("RT_LIB_PATH") and not hasattr(L, name)):
+            if (name in GEOMETRY_INPUT + RAY_QUERIES + SHADED_QUERIES + SHADED_BATCHES + TILE_LISTS + VISIBILITY +
+                    SEGMENT_QUERIES and os.environ.get("RT_LIB_PATH") and not hasattr(L, name)):
                 continue
             fn = getattr(L, name)
             fn.restype = res
@@ -383,6 +390,15 @@ def device_ray_args(a, b, device, names=("orig", "dirs")):
     directions, or points and normals): (a pointer, b pointer, n).  Both float32 [n, 3] with the same n,
     contiguous, on the GPU with index ``device``.  TypeError for a non-tensor or a wrong dtype, ValueError for
     the wrong place, layout, shape or count."""
+    # (what each tensor is, its layout included, before where it lies: a [3, n] tensor transposed has the right
+    # shape and would be read as other rays, and the mistake shows without a GPU)
+    _ray_pair_form(a, b, names)
+    for t, name in zip((a, b), names):
+        _device_place(t, name, device)
+    return a.data_ptr(), b.data_ptr(), a.shape[0]
+
+
+def _ray_pair_form(a, b, names):
     import torch
 
     for t, name in zip((a, b), names):
@@ -394,13 +410,30 @@ def device_ray_args(a, b, device, names=("orig", "dirs")):
             raise ValueError(f"{name}: shape {tuple(t.shape)}, [n, 3] is needed")
     if a.shape[0] != b.shape[0]:
         raise ValueError(f"{names[0]} has {a.shape[0]} rows, {names[1]} {b.shape[0]}")
-    # (what each tensor is, its layout included, before where it lies: a [3, n] tensor transposed has the right
-    # shape and would be read as other rays, and the mistake shows without a GPU)
     for t, name in zip((a, b), names):
         _contiguous(t, name)
-    for t, name in zip((a, b), names):
+
+
+def device_segment_args(orig, dirs, tmax, device):
+    """The checks of Renderer.occluded_device / trace_segments_device on their input tensors: (orig pointer, dirs
+    pointer, tmax pointer or None, n).  orig, dirs as device_ray_args takes them; tmax: None (+inf for every ray)
+    or a float32 tensor of one dimension and exactly n elements, contiguous, on the GPU with index ``device``.
+    What every tensor is (layout included) before where any lies, so those mistakes show without a GPU."""
+    import torch
+
+    _ray_pair_form(orig, dirs, ("orig", "dirs"))
+    n = orig.shape[0]
+    if tmax is not None:
+        if not isinstance(tmax, torch.Tensor):
+            raise TypeError(f"tmax: a torch tensor on the GPU is needed, not {type(tmax).__name__}")
+        if tmax.dtype != torch.float32:
+            raise TypeError(f"tmax: dtype {tmax.dtype}, torch.float32 is needed")
+        if tmax.dim() != 1 or tmax.shape[0] != n:
+            raise ValueError(f"tmax: shape {tuple(tmax.shape)}, [{n}] is needed (one length per ray)")
+        _contiguous(tmax, "tmax")
+    for t, name in ((orig, "orig"), (dirs, "dirs")) + (() if tmax is None else ((tmax, "tmax"),)):
         _device_place(t, name, device)
-    return a.data_ptr(), b.data_ptr(), a.shape[0]
+    return orig.data_ptr(), dirs.data_ptr(), None if tmax is None else tmax.data_ptr(), n
 
 
 def _contiguous(t, name):

@@ -481,6 +481,31 @@ int rt_get_device_ray_queries(rt_renderer* r, int64_t calls[2], int64_t rays[2])
         return RT_OK;
     });
 }
+int rt_occluded_device(rt_renderer* r, const float* d_orig, const float* d_dir, const float* d_tmax, int64_t n,
+                       uint8_t* d_occluded, int64_t* d_counts, void* hip_stream)
+{
+    return guarded(R(r), [&] {
+        return R(r)->occluded_device(d_orig, d_dir, d_tmax, n, d_occluded, d_counts, reinterpret_cast<hipStream_t>(hip_stream));
+    });
+}
+int rt_trace_segments_device(rt_renderer* r, const float* d_orig, const float* d_dir, const float* d_tmax, int64_t n,
+                             int32_t* d_tri_id, float* d_t, float* d_u, float* d_v, uint8_t* d_ret, int64_t* d_counts,
+                             void* hip_stream)
+{
+    return guarded(R(r), [&] {
+        return R(r)->trace_segments_device(d_orig, d_dir, d_tmax, n, d_tri_id, d_t, d_u, d_v, d_ret, d_counts,
+                                           reinterpret_cast<hipStream_t>(hip_stream));
+    });
+}
+int rt_get_device_segment_queries(rt_renderer* r, int64_t calls[2], int64_t rays[2])
+{
+    return guarded(R(r), [&] {
+        if (!calls || !rays)
+            return RT_EINVAL;
+        R(r)->device_segment_queries(calls, rays);
+        return RT_OK;
+    });
+}
 int rt_trace_ray_device(rt_renderer* r, const float* d_orig, const float* d_dir, int64_t n,
                         int32_t current_recursion_depth, int64_t first_ray, float* d_rgba, int32_t* d_hit_src, float* d_t,
                         uint8_t* d_found, uint8_t* d_shadowed, int64_t* d_counts, void* hip_stream)

@@ -3719,6 +3719,106 @@ __global__ __launch_bounds__(BLOCK, RT_OCC_PLAIN) void closest_rays_kernel(KPara
     }
 }
 
+// The ray-segment queries over the caller's device memory (rt_occluded_device: RECORD false, one byte per ray;
+// rt_trace_segments_device: RECORD true, closest_rays_kernel's five outputs).  With (id, t, u, v, ret) what
+// closest_rays_kernel writes for ray i, hit_i = ret != 0 && t < tmax[i] (float32, strict, false for a NaN on
+// either side; tmax null: +inf for every ray): the byte is hit_i, the record is written where hit_i holds and
+// (-1, -1, 1, 0, 0) everywhere else.  Per ray:
+//  * the wide query among hits at t <= hi = tmax (a NaN tmax: the whole line, and the comparison below is false).
+//    W_MISS: no triangle reports a hit at t <= tmax, and the reference's record is a reported hit, so hit_i is
+//    false.  A certified W_HIT: w.t <= tmax is the least reported t, the reference's record (wide_closest's
+//    argument; wide_shadow's for the t alone), so hit_i is w.t < tmax.  The occlusion query reads only that t and
+//    runs without ties, as wide_shadow does; the record needs the identity and runs with them.  A ray from the
+//    camera position reads the camera's risk words, as wide_closest does; nothing else is skipped (no risk cap,
+//    no scene bound, no origin cones, no early answer by tmax);
+//  * anything else, a NaN ray, no resident tree: the octree query, over [-m, tmax + m] with is_shadowed's
+//    seg_margin where the frames' segment queries are on (P.seg_scale > 0 && P.seg_oct; DESIGN.md 5.2: the record
+//    is unchanged where it lies inside the segment, and a record beyond tmax fails the comparison whatever it
+//    is), else over the whole line;
+//  * the brute-force loop when enable_bvh is off.
+// counts as closest_rays_kernel's: [0] += rays the certified wide query decided, [1] += the others, one atomic per
+// wave and word, so no lane leaves before the wave's ballots.
+// (RT_OCC_PLAIN for closest_rays_kernel's reason; the compiler's notes are in DESIGN.md 13.)
+template <bool RECORD>
+__global__ __launch_bounds__(BLOCK, RT_OCC_PLAIN) void segment_rays_kernel(KParams P_arg, const float* __restrict__ orig,
+                                                                           const float* __restrict__ dir,
+                                                                           const float* __restrict__ tmax, int n,
+                                                                           int32_t* __restrict__ out_id,
+                                                                           float* __restrict__ out_t, float* __restrict__ out_u,
+                                                                           float* __restrict__ out_v,
+                                                                           uint8_t* __restrict__ out_flag,
+                                                                           unsigned long long* __restrict__ counts)
+{
+    const KParams& P = kernel_params();
+    (void)P_arg;
+    uint2* lv = lane_stack();
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    bool wide = false;
+    if (i < n) {
+        const size_t j = 3 * (size_t)i;   // (in 64 bits, as closest_rays_kernel)
+        const v3 o = mk(orig[j], orig[j + 1], orig[j + 2]);
+        const v3 d = mk(dir[j], dir[j + 1], dir[j + 2]);
+        const float tm = tmax ? tmax[i] : INFINITY;
+        const float hi = tm == tm ? tm : INFINITY;
+        THit h;
+        h.t = -1.0f; h.u = 1.0f; h.v = 0.0f; h.k = -1;
+        int32_t id = -1;
+        bool r = false;
+        if (P.enable_bvh) {
+            if (P.wnodes && P.nnodes > 0 && !ray_is_nan(o, d)) {
+                const bool cam = o.x == P.cam_pos[0] && o.y == P.cam_pos[1] && o.z == P.cam_pos[2];
+                WHit w;
+                const int st = wide_run<WStackLds, 1>(P, o, d, lv, w, hi, RECORD, W_QS_CLOSEST, cam ? P.wrisk : nullptr, 0,
+                                                      0.0f, 0u, false, -1);
+                uint4 M;
+                if (st == W_MISS)
+                    wide = true;
+                else if (st == W_HIT && wide_certified(P, w, o, d, M)) {
+                    wide = true;
+                    h.t = w.t; h.u = w.u; h.v = w.v;
+                    id = (int32_t)M.z;
+                    r = true;
+                }
+            }
+            if (!wide) {
+                const bool seg = P.seg_scale > 0.0f && P.seg_oct;
+                const float m = seg ? seg_margin(P, make_ray(P, o, d)) : 0.0f;
+                const OctQ q = octree_query<false>(P, o, d, -m, hi + m, seg, lv);
+                h = q.h;
+                r = q.r;
+                id = h.k >= 0 ? P.tri_id[h.k] : -1;
+            }
+        } else {
+            const TRay R = make_ray(P, o, d);
+            for (int k = 0; k < P.ntri_slots; k++) {
+                float t, u, v;
+                if (tri_test(P.tris, (uint32_t)k, R, t, u, v))
+                    if (t < h.t || h.t == -1) {
+                        h.t = t; h.u = u; h.v = v; h.k = k;
+                    }
+            }
+            r = h.k >= 0;
+            id = r ? P.tri_id[h.k] : -1;
+        }
+        const bool hit = r && h.t < tm;
+        if (RECORD) {
+            out_id[i] = hit ? id : -1;
+            out_t[i] = hit ? h.t : -1.0f;
+            out_u[i] = hit ? h.u : 1.0f;
+            out_v[i] = hit ? h.v : 0.0f;
+        }
+        out_flag[i] = hit ? 1 : 0;
+    }
+    if (counts) {
+        const unsigned long long nw = (unsigned long long)__popcll(__ballot(wide));
+        const unsigned long long no = (unsigned long long)__popcll(__ballot(i < n && !wide));
+        if (__lane_id() == 0) {
+            if (nw) atomicAdd(&counts[0], nw);
+            if (no) atomicAdd(&counts[1], no);
+        }
+    }
+}
+
 // Renderer::is_shadowed(inter_point, normal, light_position) (renderer.cpp:340-402) for a batch of
 // (point, normal) pairs in the caller's device memory (rt_is_shadowed_device): the generic query of the
 // shaded kernels with the call's light, which reads the frame's light risk words only when that light
@@ -4113,6 +4213,24 @@ hipError_t rt_launch_shadow_points(const rt::KParams* P, const float* point, con
     size_t lds = rt::lds_bytes(*P);
     hipLaunchKernelGGL(rt::shadow_points_kernel, dim3((n + rt::BLOCK - 1) / rt::BLOCK), dim3(rt::BLOCK), lds, stream, *P,
                        point, normal, n, light[0], light[1], light[2], shadowed);
+    return hipGetLastError();
+}
+
+hipError_t rt_launch_segment_rays(const rt::KParams* P, bool record, const float* o, const float* d, const float* tmax,
+                                  int n, int32_t* id, float* t, float* u, float* v, uint8_t* flag, int64_t* counts,
+                                  hipStream_t stream)
+{
+    if (n <= 0)
+        return hipSuccess;
+    size_t lds = rt::lds_bytes(*P);
+    const dim3 grid((n + rt::BLOCK - 1) / rt::BLOCK);
+    unsigned long long* c = reinterpret_cast<unsigned long long*>(counts);
+    if (record)
+        hipLaunchKernelGGL(rt::segment_rays_kernel<true>, grid, dim3(rt::BLOCK), lds, stream, *P, o, d, tmax, n, id, t, u,
+                           v, flag, c);
+    else
+        hipLaunchKernelGGL(rt::segment_rays_kernel<false>, grid, dim3(rt::BLOCK), lds, stream, *P, o, d, tmax, n, id, t, u,
+                           v, flag, c);
     return hipGetLastError();
 }
 

@@ -51,6 +51,11 @@ RT_LAUNCH rt_launch_closest_rays(const rt::KParams* P, const float* o, const flo
                                  float* u, float* v, uint8_t* ret, int64_t* counts, hipStream_t stream);
 RT_LAUNCH rt_launch_shadow_points(const rt::KParams* P, const float* point, const float* normal, int n,
                                   const float light[3], uint8_t* shadowed, hipStream_t stream);
+// the ray-segment queries (rt_occluded_device: record false, flag = the occlusion byte, id / t / u / v unused;
+// rt_trace_segments_device: record true, flag = ret).  tmax [n] may be null: +inf for every ray
+RT_LAUNCH rt_launch_segment_rays(const rt::KParams* P, bool record, const float* o, const float* d, const float* tmax,
+                                 int n, int32_t* id, float* t, float* u, float* v, uint8_t* flag, int64_t* counts,
+                                 hipStream_t stream);
 // the visibility buffer of P's camera over the caller's device memory (rt_visibility_device): id / t [rh][rw], uv
 // [rh][rw][2] (8-byte aligned), each may be null.  fast: the plain frame kernel's primary query with P's tile mask
 // and entry sets (the host: P->wnodes, enable_bvh, no analytic shape), else the generic one.  P->counters: the

@@ -2873,6 +2873,39 @@ int Renderer::is_shadowed_device(const float* d_point, const float* d_normal, in
     return end_ray_query(Q_SHADOW, n, stream);
 }
 
+// The ray-segment queries (rt_occluded_device, rt_trace_segments_device): trace_rays_device's start
+// and end around segment_rays_kernel; d_tmax and d_counts may be null
+int Renderer::occluded_device(const float* d_orig, const float* d_dir, const float* d_tmax, int64_t n,
+                              uint8_t* d_occluded, int64_t* d_counts, hipStream_t stream)
+{
+    const void* const ptrs[] = {d_orig, d_dir, d_occluded, d_tmax, d_counts};
+    KParams P;
+    int rc = begin_ray_query("occluded_device", ptrs, 5, 3, n, stream, P);
+    if (rc != RT_OK || n == 0)
+        return rc;
+    hipError_t e = rt_launch_segment_rays(&P, false, d_orig, d_dir, d_tmax, (int)n, nullptr, nullptr, nullptr, nullptr,
+                                          d_occluded, d_counts, stream);
+    if (e != hipSuccess)
+        return hip_fail(e, "segment_rays_kernel launch");
+    return end_ray_query(Q_OCCLUDED, n, stream);
+}
+
+int Renderer::trace_segments_device(const float* d_orig, const float* d_dir, const float* d_tmax, int64_t n,
+                                    int32_t* d_id, float* d_t, float* d_u, float* d_v, uint8_t* d_ret,
+                                    int64_t* d_counts, hipStream_t stream)
+{
+    const void* const ptrs[] = {d_orig, d_dir, d_id, d_t, d_u, d_v, d_ret, d_tmax, d_counts};
+    KParams P;
+    int rc = begin_ray_query("trace_segments_device", ptrs, 9, 7, n, stream, P);
+    if (rc != RT_OK || n == 0)
+        return rc;
+    hipError_t e = rt_launch_segment_rays(&P, true, d_orig, d_dir, d_tmax, (int)n, d_id, d_t, d_u, d_v, d_ret, d_counts,
+                                          stream);
+    if (e != hipSuccess)
+        return hip_fail(e, "segment_rays_kernel launch");
+    return end_ray_query(Q_SEGMENTS, n, stream);
+}
+
 // The visibility buffer of the current camera (rt_visibility_device).  The ray queries' start and end
 // (the pointer check, the scene as a frame brings it up to date, the risk words, query_fence_), and between them
 // what a frame launch prepares, from a slot of the launching stream's own: the tile queue's counter block and the
@@ -2972,6 +3005,12 @@ void Renderer::device_visibility(int64_t calls[2], int64_t pixels[2], int64_t us
     used[0] = vis_used_[0];
     used[1] = vis_used_[1];
 }
+
+void Renderer::device_segment_queries(int64_t calls[2], int64_t rays[2]) const
+{
+    copy_kinds(query_calls_, query_rays_, Q_OCCLUDED, 2, calls, rays);
+}
+static_assert(Q_SEGMENTS == Q_OCCLUDED + 1, "rt_get_device_segment_queries reports the two kinds as a run");
 
 static_assert(Q_SHADOW == Q_CLOSEST + 1 && Q_SHADED_GENERIC == Q_SHADED_PLAIN + SHADE_GENERIC &&
                   Q_SHADED_REFL == Q_SHADED_PLAIN + SHADE_REFL && Q_BATCH_DELEGATED == Q_BATCH_ENGINE + 1 &&

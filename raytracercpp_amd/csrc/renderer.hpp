@@ -205,6 +205,8 @@ enum QueryKind {
     Q_BATCH_DELEGATED,   // ... handed to trace_ray_device's code (counted there too)
     Q_VISIBILITY_FAST,     // visibility_device by instance of visibility_kernel (the "rays": pixels)
     Q_VISIBILITY_GENERIC,
+    Q_OCCLUDED,          // occluded_device
+    Q_SEGMENTS,          // trace_segments_device
     Q_KINDS,
     Q_NONE = -1,         // nothing was launched for the scene's rays: an empty call, or the fill past the depth limit
 };
@@ -326,6 +328,15 @@ public:
                            uint8_t* d_shadowed, hipStream_t stream);
     // launches of the two kernels since rt_create and the rays given to them (rt_get_device_ray_queries)
     void device_ray_queries(int64_t calls[2], int64_t rays[2]) const;
+    // The ray-segment queries (rt_occluded_device, rt_trace_segments_device): with trace_rays_device's
+    // (id, t, u, v, ret) for ray i, hit_i = ret && t < d_tmax[i] (d_tmax null: +inf); the byte hit_i, or the record
+    // where hit_i holds and (-1, -1, 1, 0, 0) elsewhere.  trace_rays_device's contract otherwise.
+    int occluded_device(const float* d_orig, const float* d_dir, const float* d_tmax, int64_t n, uint8_t* d_occluded,
+                        int64_t* d_counts, hipStream_t stream);
+    int trace_segments_device(const float* d_orig, const float* d_dir, const float* d_tmax, int64_t n, int32_t* d_id,
+                              float* d_t, float* d_u, float* d_v, uint8_t* d_ret, int64_t* d_counts, hipStream_t stream);
+    // their launches and rays since rt_create: occluded, segments (rt_get_device_segment_queries)
+    void device_segment_queries(int64_t calls[2], int64_t rays[2]) const;
     // Renderer::trace_ray (shaded) over q's rays in memory of device_, on the caller's stream (rt_trace_ray_device)
     int trace_ray_device(const ShadeRays& q, hipStream_t stream) { return shade_rays_device("trace_ray_device", q, stream); }
     // its launches and rays since rt_create by instance: plain, generic, reflective (rt_get_device_shaded_queries)

@@ -473,6 +473,52 @@ class Renderer:
         self._call("rt_get_device_ray_queries", ptr(calls, i64p), ptr(rays, i64p))
         return (int(calls[0]), int(calls[1])), (int(rays[0]), int(rays[1]))
 
+    # -- ray-segment queries on GPU memory (include/rt_mi355x.h "Ray-segment queries on device memory") ------
+    def occluded_device(self, orig, dirs, tmax=None, out=None, counts=None, stream=None):
+        """rt_occluded_device: is anything hit before tmax[i] along ray i -> a uint8 torch tensor [n], 1 where
+        trace_rays_device's answer for the ray has ret != 0 and t < tmax[i] (float32, strict, false for a NaN).
+        orig, dirs, counts, stream as in trace_rays_device; tmax: a contiguous float32 [n] tensor on this
+        renderer's GPU, None = +inf for every ray; out: a uint8 tensor of at least n elements to write into."""
+        import torch
+        op, dp, tp, n = _lib.device_segment_args(orig, dirs, tmax, self.device)
+        if n > 1 << 30:
+            raise ValueError(f"occluded_device: {n} rays, at most 2^30 are taken")
+        stream = self._ray_stream(stream)
+        if out is None:
+            with torch.cuda.stream(stream):
+                out = torch.empty(n, dtype=torch.uint8, device=orig.device)
+        sp = _lib.device_ray_out(out, "out", torch.uint8, n, self.device)
+        cp = None if counts is None else _lib.device_ray_out(counts, "counts", torch.int64, 2, self.device)
+        self._call("rt_occluded_device", C.c_void_p(op), C.c_void_p(dp), C.c_void_p(tp), n, C.c_void_p(sp),
+                   C.c_void_p(cp), self._stream_ptr(stream, self.device))
+        return out
+
+    def trace_segments_device(self, orig, dirs, tmax=None, out=None, counts=None, stream=None):
+        """rt_trace_segments_device: trace_rays_device's dict where the ray's answer has ret != 0 and
+        t < tmax[i], bit for bit, and (-1, -1.0, 1.0, 0.0, 0) everywhere else.  tmax as in occluded_device, the
+        other arguments as in trace_rays_device."""
+        import torch
+        op, dp, tp, n = _lib.device_segment_args(orig, dirs, tmax, self.device)
+        if n > 1 << 30:
+            raise ValueError(f"trace_segments_device: {n} rays, at most 2^30 are taken")
+        stream = self._ray_stream(stream)
+        if out is None:
+            with torch.cuda.stream(stream):
+                out = {k: torch.empty(n, dtype=getattr(torch, dt), device=orig.device) for k, dt in self._RAY_OUT}
+        ptrs = [_lib.device_ray_out(out[k], k, getattr(torch, dt), n, self.device) for k, dt in self._RAY_OUT]
+        cp = None if counts is None else _lib.device_ray_out(counts, "counts", torch.int64, 2, self.device)
+        self._call("rt_trace_segments_device", C.c_void_p(op), C.c_void_p(dp), C.c_void_p(tp), n,
+                   *[C.c_void_p(p) for p in ptrs], C.c_void_p(cp), self._stream_ptr(stream, self.device))
+        return out
+
+    def device_segment_queries(self):
+        """rt_get_device_segment_queries -> (calls, rays): launches of occluded_device and of
+        trace_segments_device since the renderer was created, and the rays given to them (two ints each)."""
+        calls, rays = np.zeros(2, np.int64), np.zeros(2, np.int64)
+        i64p = C.POINTER(C.c_int64)
+        self._call("rt_get_device_segment_queries", ptr(calls, i64p), ptr(rays, i64p))
+        return (int(calls[0]), int(calls[1])), (int(rays[0]), int(rays[1]))
+
     def visibility_device(self, out=None, stream=None):
         """rt_visibility_device: the visibility buffer of the current camera, in the order of ``stream`` (a torch
         stream; default the current one) and without a host wait -> dict(tri_id int32 [rh, rw], t float32 [rh, rw],
